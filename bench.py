@@ -34,7 +34,16 @@ Two ingest modes:
 50K-word multi-script one (~200K active bigrams per batch: the tiered SGD
 layout).
 
-Usage:  python bench.py [--gpus N --steps K --warmup W] [--prepacked] [--profile wide]
+A plain run sets up, warms up, times the steps and prints the result line.
+``--full`` adds what the headline figure does not need: the pinned
+host-to-device bandwidth measurement (``h2d_gbps``, ``h2d_floor_ms_per_step``)
+and the bit-identical-replicas check of the final model.  ``--dump-outputs
+DIR`` writes what the last timed step computed (the model, the batch's
+prequential stats, loss history and counts) as ``DIR/<name>.npy``: the inputs
+are seeded, so two builds can be compared output for output.
+
+Usage:  python bench.py [--gpus N --steps K --warmup W] [--prepacked] [--profile wide] [--full]
+        [--dump-outputs DIR]
         (N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...)
 """
 from __future__ import annotations
@@ -110,9 +119,60 @@ def parse_args(argv=None):
                     help="local[N]: BASELINE config 1 -- the fp64 CPU engine (oracle/mllib.py semantics, "
                          "what the reference's --master local[2] runs) on the same synthetic data, N host "
                          "threads (one stands for the receiver, as in Spark local mode); no GPU is used")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the pinned host-to-device "
+                         "bandwidth measurement behind h2d_gbps / h2d_floor_ms_per_step and the "
+                         "replicas_identical check of the final model (a plain run sets up, warms up, times "
+                         "the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed -- the model and "
+                         "the batch results a caller of the engine receives -- as DIR/<name>.npy (float64)")
     ap.add_argument("--json-out", default="")
     ap.add_argument("--verbose", action="store_true")
     return ap.parse_args(argv)
+
+
+# Result fields of the last timed step that are counts or sums of the batch
+# (not clocks): written by --dump-outputs as batch_results.npy, in this order.
+LR_RESULT_FIELDS = ("n_raw", "n_kept", "n_kept_global", "n_unique", "entries", "iterations", "converged",
+                    "diverged", "rows_lowered", "rows_narrowed", "tiered", "n_near")
+KM_RESULT_FIELDS = ("n_raw", "n_local", "n")
+DUMP_MAX_VALUES = 4 << 20   # float64 values per dumped array (32 MB)
+
+
+def dump_outputs(out_dir: str, eng, is_km: bool, res) -> None:
+    """--dump-outputs: the arrays a caller of the timed path holds after its
+    last step, as float64 ``.npy`` files.  LR: ``weights`` (the model, F + 4),
+    ``stats`` (the prequential sums n, sum y, sum y^2, sum p, sum p^2, sum
+    (y-p)^2 of the batch), ``loss_history`` and ``batch_results``
+    (LR_RESULT_FIELDS).  k-means: ``centers`` (k x d), ``cluster_weights``
+    (k), ``std`` (the batch's scaler) and ``batch_results``
+    (KM_RESULT_FIELDS).  8 MB at 1M features; a model of more than
+    DUMP_MAX_VALUES weights is written as a fixed sample (``weights_index``
+    holds the sampled positions), under 50 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    res = res or {}
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    fields = KM_RESULT_FIELDS if is_km else LR_RESULT_FIELDS
+    save("batch_results", [float(res.get(k, 0) or 0) for k in fields])
+    if is_km:
+        c, w = eng.get_state()
+        save("centers", c)
+        save("cluster_weights", w)
+        if res.get("std") is not None:
+            save("std", res["std"])
+    else:
+        w = np.asarray(eng.get_weights())
+        if w.size > DUMP_MAX_VALUES:   # a fixed, seeded sample of a model past 32 MB (config 5: 100M weights)
+            idx = np.unique(np.random.default_rng(20240229).integers(0, w.size, DUMP_MAX_VALUES // 2))
+            save("weights_index", idx)
+            w = w[idx]
+        save("weights", w)
+        save("stats", res.get("stats", []))
+        save("loss_history", res.get("loss_history", []))
 
 
 class Runner:
@@ -127,6 +187,7 @@ class Runner:
         self.marks = []           # (sealed, done) host clock per timed batch
         self.phases = []          # the engine's per-batch host / device phase times (LR)
         self.hang_at = 0          # TWTML_BENCH_HANG=<rank>:<step>: that rank hangs before that step
+        self.last = None          # the engine's result of the last timed batch (--dump-outputs)
 
     def process(self, slot: int):
         self.steps_done += 1
@@ -140,6 +201,7 @@ class Runner:
     def record(self, res, sealed: float, done: float) -> None:
         self.lat.append((done - sealed) * 1e3)
         self.marks.append((sealed, done))
+        self.last = res
         if self.is_km:
             self.kept.append(res["n_local"])
             self.stage.append((res["ms"], 0.0))
@@ -319,6 +381,42 @@ def hbm_batch(args, synth, device: int, ingest: str):
                "hbm_max_rows": rows, "batch_cap": args.batch_cap}
 
 
+def utf8_pool(synth, B: int, n_pool: int, now_ms: int):
+    """The pool of the default ingest: batch i is ``generate_batch(synth, i *
+    B, B)`` with its text kept as the receiver's page-locked UTF-8 bytes
+    only.  The UTF-16 text is generated into two reused buffers, batch i + 1
+    while batch i is encoded and registered, so set-up neither holds nor
+    copies the pool's UTF-16.  Returns (batches, their Utf8Text, pinned bytes)."""
+    import concurrent.futures as cf
+    from twitter_stream_ml_amd.ops._native import host
+    from twitter_stream_ml_amd.ops.lr_engine import encode_utf8, register_host
+    from twitter_stream_ml_amd.records.batch import RawBatch
+    from twitter_stream_ml_amd.sources.synthetic import generate_into
+    cap = int(host().synth_max_units(synth.as_params(), B))
+    scratch = [np.empty(cap, np.uint16) for _ in range(min(2, n_pool))]
+
+    def gen(i):
+        text = scratch[i % 2]
+        offsets, is_rt, scalars = np.empty(B + 1, np.int64), np.empty(B, np.uint8), np.empty((5, B), np.int64)
+        used = generate_into(synth, i * B, B, text, offsets, is_rt, scalars)
+        return RawBatch(text[:used], offsets, is_rt, scalars, now_ms)
+
+    pool, u8s, pinned = [], [], 0
+    with cf.ThreadPoolExecutor(max_workers=1) as ex:
+        nxt = ex.submit(gen, 0)
+        for i in range(n_pool):
+            r = nxt.result()
+            if i + 1 < n_pool:
+                nxt = ex.submit(gen, i + 1)
+            u = encode_utf8(r)   # the receiver's UTF-8 buffer (as the network delivered it)
+            register_host(u.data)
+            pinned += int(u.data.nbytes)
+            u8s.append(u)
+            pool.append(RawBatch(np.zeros(0, np.uint16), r.offsets, r.is_retweet, r.scalars, r.batch_time_ms,
+                                 utf8=u))
+    return pool, u8s, pinned
+
+
 def final_model(eng, is_km: bool) -> np.ndarray:
     """The replicated model state every DP rank must hold bit for bit."""
     if is_km:
@@ -407,6 +505,8 @@ def run_cpu_local(args) -> int:
             kept.append(res["n_kept"])
             iters.append(res["iterations"])
     t1 = time.perf_counter()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, False, res)
     value = float(sum(kept)) / (t1 - t0)
     out = {
         "metric": "tweets/sec trained (whole node)",
@@ -496,9 +596,16 @@ def main(argv=None) -> int:
     n_pool = args.pool if args.pool > 0 else args.warmup + args.steps
     if args.pool <= 0:   # fresh batches for every step, within a host-memory budget of pooled tweets
         n_pool = max(1, min(n_pool, int(os.environ.get("TWTML_BENCH_POOL_TWEETS", "64000000")) // max(1, B)))
-    pool_raw = [generate_batch(synth, i * B, B, batch_time_ms=now_ms) for i in range(n_pool)]
-    max_units = max(r.total_units for r in pool_raw) + 1024
     is_km = args.model == "kmeans"
+    u8s = []
+    pinned = 0   # bytes of page-locked host memory this rank holds (staging views + registered pool)
+    # the default ingest keeps only each batch's UTF-8 bytes: they are made as the batch is generated
+    pool_is_utf8 = args.e2e and ingest == "utf8" and not (is_km and args.text_dims == 0)
+    if pool_is_utf8:
+        pool_raw, u8s, pinned = utf8_pool(synth, B, n_pool, now_ms)
+    else:
+        pool_raw = [generate_batch(synth, i * B, B, batch_time_ms=now_ms) for i in range(n_pool)]
+    max_units = max(r.total_units for r in pool_raw) + 1024
     if is_km:
         from twitter_stream_ml_amd.ops.kmeans_engine import DeviceKMeans, KMDeviceConfig
         kcfg = KMDeviceConfig(k=args.k, text_dims=args.text_dims, half_life=5.0, max_rows=B,
@@ -507,8 +614,6 @@ def main(argv=None) -> int:
     else:
         eng = DeviceLinearRegression(lr_config(args, B, max_units, ingest, dp=comm is not None), device=device,
                                      comm=comm)
-    u8s = []
-    pinned = 0   # bytes of page-locked host memory this rank holds (staging views + registered pool)
     if args.e2e:
         # utf8 / utf16 ingest DMAs the text from the receiver's registered
         # buffers: the staging views hold row words and scalars only
@@ -520,15 +625,6 @@ def main(argv=None) -> int:
         if ingest == "utf8" and is_km and args.text_dims == 0:   # 2 scalar features: no text needed
             from twitter_stream_ml_amd.ops.kmeans_engine import no_text
             u8s = [no_text(r) for r in pool_raw]
-        elif ingest == "utf8":   # the receiver's UTF-8 buffers (as the network delivered them)
-            u8s = [encode_utf8(r) for r in pool_raw]
-            for u in u8s:
-                register_host(u.data)
-                pinned += int(u.data.nbytes)
-            # the UTF-16 copy is not staged in this mode: drop it (the batch
-            # carries the receiver's UTF-8 buffer instead)
-            pool_raw = [RawBatch(np.zeros(0, np.uint16), r.offsets, r.is_retweet, r.scalars, r.batch_time_ms,
-                                 utf8=u) for r, u in zip(pool_raw, u8s)]
         elif ingest == "utf16":
             for r in pool_raw:   # the receiver's buffers: DMA source of the text
                 register_host(r.text)
@@ -579,8 +675,10 @@ def main(argv=None) -> int:
         t0, t1 = run_e2e(runner, pool_raw, u8s, views, ingest, args.warmup, args.steps, sync)
     else:
         t0, t1 = run_device_pipeline(runner, pool, args.warmup, args.steps, sync)
-    # DP replicas must be bit-identical after the run (SURVEY §5 race detection)
-    replicas = D.replicas_identical(final_model(eng, is_km))
+    if args.dump_outputs and info.is_main:
+        dump_outputs(args.dump_outputs, eng, is_km, runner.last)
+    # --full: DP replicas must be bit-identical after the run (SURVEY §5 race detection)
+    replicas = D.replicas_identical(final_model(eng, is_km)) if args.full else None
     elapsed = D.allreduce_max_scalar(t1 - t0)
     tweets = D.allreduce_sum_scalar(float(sum(runner.kept)))
     p50 = D.allreduce_max_scalar(float(np.median(runner.lat)))
@@ -589,10 +687,10 @@ def main(argv=None) -> int:
     mine = float(sum(runner.kept)) / max(t1 - t0, 1e-12)   # this rank's own tweets/s over its window
     per_rank = D.gather_to_main(np.array([mine]))
     prestaged = int(D.allreduce_max_scalar(float(runner.prestaged_at_t0)))
-    # host-link floor: the timed window's H2D bytes (engine counter) over this
-    # box's pinned host-to-device bandwidth (measured here, after the window)
+    # --full: host-link floor: the timed window's H2D bytes (engine counter) over
+    # this box's pinned host-to-device bandwidth (measured here, after the window)
     moved = float(h2d.get("b1", 0) - h2d.get("b0", 0))
-    gbps = D.allreduce_min_scalar(_h2d_gbps(device))
+    gbps = D.allreduce_min_scalar(_h2d_gbps(device)) if args.full else None
     import resource
     rss_mb = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
     host = D.gather_to_main(np.array([rss_mb, pinned / 2**20, t_gen]))   # per rank, to rank 0
@@ -668,8 +766,10 @@ def main(argv=None) -> int:
     out["raw_slots"] = int(eng.raw_slots)
     if moved > 0:
         out["h2d_bytes_per_tweet"] = round(moved / (args.steps * B), 1)
-        out["h2d_gbps"] = round(gbps, 1)
-        out["h2d_floor_ms_per_step"] = round(moved / args.steps / (gbps * 1e9) * 1e3, 3) if gbps > 0 else None
+        if gbps is not None:
+            out["h2d_gbps"] = round(gbps, 1)
+            out["h2d_floor_ms_per_step"] = (round(moved / args.steps / (gbps * 1e9) * 1e3, 3)
+                                            if gbps > 0 else None)
     # TWTML_H2D_TIMING=1 (diagnostics): the copy stream's busy time and gaps
     # over the timed batches (their submits are the last args.steps ones)
     native = getattr(eng, "_eng", None)
@@ -713,7 +813,8 @@ def main(argv=None) -> int:
         out["allreduce_bytes_per_iter"] = int(round(sum(c[2] for c in runner.comm) / n_ar))
         # gradient all-reduce time per timed step (max over ranks): the DP cost model's check
         out["comm_ms_per_step"] = round(D.allreduce_max_scalar(sum(c[1] for c in runner.comm) / len(runner.comm)), 3)
-    out["replicas_identical"] = bool(replicas)
+    if replicas is not None:
+        out["replicas_identical"] = bool(replicas)
     if comm is not None:
         out["rccl_version"] = rccl_version()
         out["comm_env"] = {k: v for k, v in sorted(os.environ.items())

@@ -161,7 +161,7 @@ def test_torchrun_bench_gloo(hip_module, nproc):
     The JSON carries what a first real multi-GPU run needs to be diagnosed
     (VERDICT r4 #2): per-iteration all-reduce time and bytes, the RCCL
     version and NCCL_/RCCL_ environment, and the end-of-run replica check."""
-    p = _torchrun_bench(nproc, ["--batch", "100000", "--steps", "3", "--warmup", "1", "--pool", "2"])
+    p = _torchrun_bench(nproc, ["--batch", "100000", "--steps", "3", "--warmup", "1", "--pool", "2", "--full"])
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
