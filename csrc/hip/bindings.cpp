@@ -394,7 +394,9 @@ PYBIND11_MODULE(_twtml_hip, m) {
         std::vector<int64_t> counters, cbase;
         std::vector<int32_t> clen8, idx, perm, uniq;
         std::vector<float> y, num;
-        e.debug_prepared(counters, clen8, cbase, idx, perm, y, num, uniq);
+        std::vector<uint8_t> cfast;
+        std::vector<int32_t> nnz;
+        e.debug_prepared(counters, clen8, cbase, idx, perm, y, num, uniq, cfast, nnz);
         py::dict d;
         d["counters"] = py::array_t<int64_t>(py::ssize_t(counters.size()), counters.data());
         d["clen8"] = py::array_t<int32_t>(py::ssize_t(clen8.size()), clen8.data());
@@ -404,6 +406,8 @@ PYBIND11_MODULE(_twtml_hip, m) {
         d["y"] = py::array_t<float>(py::ssize_t(y.size()), y.data());
         d["num"] = py::array_t<float>(py::ssize_t(num.size()), num.data());
         d["uniq"] = py::array_t<int32_t>(py::ssize_t(uniq.size()), uniq.data());
+        d["cfast"] = py::array_t<uint8_t>(py::ssize_t(cfast.size()), cfast.data());
+        d["nnz"] = py::array_t<int32_t>(py::ssize_t(nnz.size()), nnz.data());
         return d;
       })
       .def("debug_merged", [](const LREngine& e) {

@@ -1562,7 +1562,8 @@ void LREngine::debug_hybrid(std::vector<int32_t>& hot_slot, std::vector<uint32_t
 void LREngine::debug_prepared(std::vector<int64_t>& counters, std::vector<int32_t>& clen8,
                               std::vector<int64_t>& cbase, std::vector<int32_t>& idx,
                               std::vector<int32_t>& perm, std::vector<float>& y,
-                              std::vector<float>& num, std::vector<int32_t>& uniq) {
+                              std::vector<float>& num, std::vector<int32_t>& uniq,
+                              std::vector<uint8_t>& cfast, std::vector<int32_t>& nnz) {
   TWTML_HIP_CHECK(hipSetDevice(device_));
   TWTML_HIP_CHECK(hipStreamSynchronize(compute_));
   TWTML_HIP_CHECK(hipStreamSynchronize(pstream_));
@@ -1579,7 +1580,11 @@ void LREngine::debug_prepared(std::vector<int64_t>& counters, std::vector<int32_
   y.resize(size_t(R));
   num.resize(size_t(4 * R));
   uniq.resize(size_t(nu));
+  cfast.resize(size_t(C));
+  nnz.resize(size_t(nk));
   if (C) {
+    TWTML_HIP_CHECK(hipMemcpy(cfast.data(), lp.cfast, size_t(C), hipMemcpyDeviceToHost));
+    TWTML_HIP_CHECK(hipMemcpy(nnz.data(), lp.nnz, sizeof(int32_t) * size_t(nk), hipMemcpyDeviceToHost));
     TWTML_HIP_CHECK(hipMemcpy(clen8.data(), lp.clen8, sizeof(int32_t) * size_t(C), hipMemcpyDeviceToHost));
     TWTML_HIP_CHECK(hipMemcpy(cbase.data(), lp.cbase, sizeof(int64_t) * size_t(C), hipMemcpyDeviceToHost));
     TWTML_HIP_CHECK(hipMemcpy(perm.data(), lp.perm, sizeof(int32_t) * size_t(R), hipMemcpyDeviceToHost));

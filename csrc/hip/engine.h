@@ -267,10 +267,13 @@ class LREngine {
   void synchronize();
   int device() const { return device_; }
   // Debug/test access to the last batch's prepared features (host copies).
+  // cfast: per chunk, 1 = the narrow fast featurizer's chunk; nnz: per kept
+  // row, bigram count in bits 0..29, wide flag in bit 30 (featurize.hip).
   void debug_prepared(std::vector<int64_t>& counters, std::vector<int32_t>& clen8,
                       std::vector<int64_t>& cbase, std::vector<int32_t>& idx,
                       std::vector<int32_t>& perm, std::vector<float>& y,
-                      std::vector<float>& num, std::vector<int32_t>& uniq);
+                      std::vector<float>& num, std::vector<int32_t>& uniq,
+                      std::vector<uint8_t>& cfast, std::vector<int32_t>& nnz);
   // Merged (slot, count) layout the iteration kernels read (empty if not merged).
   void debug_merged(std::vector<int32_t>& slot, std::vector<int32_t>& cnt,
                     std::vector<int32_t>& clen8d) const;

@@ -86,6 +86,58 @@ def test_kmeans_matches_cpu(hip_module, k, text_dims, mfma, precision):
             cpu.set_state(*dev.get_state())
 
 
+@pytest.mark.parametrize("k,text_dims,mfma", [(3, 0, True), (3, 0, False), (3, 8, True), (3, 8, False),
+                                               (64, 0, True), (64, 8, True)])
+def test_kmeans_tiny_batches(hip_module, k, text_dims, mfma):
+    """Batches of 1, 2, 3, k - 1, k, k + 1 points (fewer points than clusters)
+    and one with a constant followers column after an ordinary 4000-row one:
+    the per-batch scaler's ``n > 1 && num > 0`` guard (kmeans_engine.cpp) --
+    one point gives std == 0 in every column, a zero-variance column std == 0
+    and scale factor 0 -- and, with text dims, rows of 0 / 1 / 2 units (bigram
+    count ``len >= 2 ? len - 1 : len``, kmeans.hip).  Scaler, update and
+    prediction against the fp64 CpuKMeans with the bounds of
+    test_kmeans_matches_cpu."""
+    import edge_batches as eb
+    from twitter_stream_ml_amd.ops.kmeans_engine import DeviceKMeans
+    dev = DeviceKMeans(_cfg(k, text_dims, mfma=mfma, seed=5), device=0)
+    cpu = CpuKMeans(k, 2 + text_dims, seed=5)
+    synth = SynthConfig.profile("twitter", seed=27, unicode_fraction=0.2)
+    batches = [(None, generate_batch(synth, 0, 4000, batch_time_ms=NOW))]
+    for i, m in enumerate(sorted({1, 2, 3, k - 1, k, k + 1})):
+        batches.append((m, eb.kmeans_tiny_batch(synth, m, 10000 + 400 * i, short_texts=text_dims > 0)))
+    batches.append((5, eb.kmeans_tiny_batch(synth, 5, 20000, equal_followers=True)))
+    for m, raw in batches:
+        c_old = cpu.state.centers.copy()
+        r = dev.update_raw(raw)
+        X, _ = kmeans_features(raw, text_dims)
+        rc = cpu.update_batch(X)
+        assert r["n"] == rc["n"] == X.shape[0] == r["n_local"]
+        if m is not None:
+            assert r["n"] == m
+        np.testing.assert_allclose(r["std"], rc["std"], rtol=1e-6)
+        if m == 1:
+            assert not np.any(np.asarray(r["std"])) and not np.any(rc["std"])
+        if m == 5:
+            assert np.asarray(r["std"])[1] == 0 and np.asarray(r["std"])[0] > 0
+        Xs = rc["scaled"]
+        c_new = dev.get_state()[0]
+        want = find_closest(c_new, Xs)
+        pred = np.asarray(r["pred"])
+        assert pred.shape == want.shape
+        mismatch = np.count_nonzero((pred != want) & _well_conditioned(Xs, c_new))
+        assert mismatch <= 2, mismatch
+        if m is not None:   # a handful of points: none may differ where fp32 resolves the gap
+            assert not np.any((pred != want) & _well_conditioned(Xs, c_new, rel=1e-5)), (m, pred, want)
+        n_ill = np.count_nonzero(~_well_conditioned(Xs, c_old))
+        if n_ill == 0:
+            _check_state(dev, cpu)
+        else:
+            w_dev = dev.get_state()[1]
+            np.testing.assert_allclose(w_dev.sum(), cpu.state.weights.sum(), rtol=1e-9)
+            assert np.abs(w_dev - cpu.state.weights).sum() <= 2 * n_ill + 1e-6
+            cpu.set_state(*dev.get_state())
+
+
 def test_kmeans_points_unit_and_set_state(hip_module):
     from twitter_stream_ml_amd.ops.kmeans_engine import DeviceKMeans
     dev = DeviceKMeans(_cfg(4, 0, time_unit="points", seed=9), device=0)

@@ -12,6 +12,8 @@ from twitter_stream_ml_amd.oracle import (featurize_batch, round_half_up_array,
                                           run_minibatch_sgd)
 from twitter_stream_ml_amd.sources.synthetic import SynthConfig, generate_batch
 
+from layout_decode import hybrid_row_counts, rows_from_debug as _rows_from_debug
+
 pytestmark = pytest.mark.gpu
 
 NOW = 1_700_000_000_000
@@ -22,26 +24,6 @@ def _engine(F, hash="java", **kw):
     kw = {"max_rows": 8192, "max_units": 8192 * 300, **kw}
     cfg = LRDeviceConfig(num_text_features=F, hash=hash, **kw)
     return DeviceLinearRegression(cfg, device=0)
-
-
-def _rows_from_debug(dbg):
-    """Per kept row (kept order) -> sorted multiset of hashed feature ids.
-
-    SELL-16x4 layout: chunk c = 16 rows, row r owns lanes 4r..4r+3.
-    """
-    nk = int(dbg["counters"][0])
-    idx, clen8, cbase, perm = dbg["idx"], dbg["clen8"], dbg["cbase"], dbg["perm"]
-    rows = [None] * nk
-    for c in range(clen8.shape[0]):
-        g0, L8 = int(cbase[c]), int(clen8[c])
-        block = idx[g0 * 512:(g0 + L8) * 512].reshape(L8, 64, 8)
-        for r in range(16):
-            k = int(perm[c * 16 + r])
-            if k < 0:
-                continue
-            v = block[:, 4 * r:4 * r + 4, :].reshape(-1)
-            rows[k] = np.sort(v[v >= 0])
-    return rows
 
 
 def _with_long_row(raw, k=3, n_units=9000):
@@ -355,30 +337,15 @@ def test_hybrid_layout_matches_hashingtf(hip_module, F, hash, repeats, lazy):
     fb = featurize_batch(raw, F, 100, 1000, now_ms=NOW, hash=hash)
     Xt = fb.X[:, :F].tocsr()
     perm, cbase, clen8 = dbg["perm"], dbg["cbase"], dbg["clen8"]
-    dense = hy["hot_dense"].reshape(-1, 64, 4)
-    cslot = hy["cslot"]
     big = 0
     for c in range(hy["clen8c"].shape[0]):
         L4c = int(hy["clen8c"][c])            # cold 4-entry groups per lane
         assert 0 <= L4c <= 2 * int(clen8[c])
-        g0 = int(cbase[c])
-        blk = cslot[g0 * 512:g0 * 512 + L4c * 256].reshape(L4c, 64, 4)
         for r in range(16):
             k = int(perm[c * 16 + r])
             if k < 0:
                 continue
-            got = {}
-            for t in range(4):
-                words = dense[c, 4 * r + t]
-                for i in range(32):
-                    n = (int(words[i // 8]) >> (4 * (i % 8))) & 15
-                    if n:
-                        fid = int(uniq[hot_slot[32 * t + i] - 4])
-                        got[fid] = got.get(fid, 0) + n
-            sl = blk[:, 4 * r:4 * r + 4, :].reshape(-1)
-            sl = sl[(sl >= 4) & (sl < 4 + nU)]
-            for fid in uniq[sl - 4].tolist():
-                got[fid] = got.get(fid, 0) + 1
+            got = hybrid_row_counts(hy, uniq, cbase, c, r)
             a, b = Xt.indptr[k], Xt.indptr[k + 1]
             want = dict(zip(Xt.indices[a:b].tolist(), Xt.data[a:b].astype(int).tolist()))
             big += sum(1 for v in want.values() if v > 15)
