@@ -139,6 +139,8 @@ PYBIND11_MODULE(_twtml_hip, m) {
   m.def("rccl_version", &rccl_version);
   // device bytes allocated by the engines so far (monotonic; HBM batch sizing)
   m.def("device_bytes_allocated", [] { return uint64_t(dev_alloc_bytes().load()); });
+  // ... of which not released yet: back at its earlier value once the engines built since are gone
+  m.def("device_bytes_live", [] { return uint64_t(dev_live_bytes().load()); });
 
   py::class_<Comm, std::shared_ptr<Comm>>(m, "CommBase")
       .def_property_readonly("rank", &Comm::rank)
@@ -162,11 +164,9 @@ PYBIND11_MODULE(_twtml_hip, m) {
       // link checks).  The engines issue their collectives on their own streams.
       .def("allreduce_f64", [](Comm& c, uintptr_t dev_ptr, size_t count) {
         py::gil_scoped_release nogil;
-        hipStream_t s;
-        TWTML_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        Stream s(hipStreamNonBlocking);
         c.allreduce(reinterpret_cast<void*>(dev_ptr), count, ncclFloat64, ncclSum, s);
         TWTML_HIP_CHECK(hipStreamSynchronize(s));
-        TWTML_HIP_CHECK(hipStreamDestroy(s));
         c.check_async();
       }, py::arg("dev_ptr"), py::arg("count"));
   // RCCL communicator (one process per GPU)
@@ -237,7 +237,7 @@ PYBIND11_MODULE(_twtml_hip, m) {
       })
       .def_property_readonly("spack_bytes", [](py::object self) {   // the packed scalar columns (tests)
         auto& h = self.cast<HostBatch&>();
-        const size_t cap = static_cast<const uint8_t*>(h.base) + h.bytes - h.spack;
+        const size_t cap = static_cast<const uint8_t*>(h.base.get()) + h.bytes - h.spack;
         return view<uint8_t>(h.spack, {py::ssize_t(cap)}, self);
       })
       .def("pack_rows", [](HostBatch& h, int64_t n) {

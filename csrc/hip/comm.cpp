@@ -211,15 +211,10 @@ HostComm::HostComm(int rank, int world, Fn fn) : fn_(std::move(fn)) {
   world_ = world;
 }
 
-HostComm::~HostComm() {
-  if (host_) (void)hipHostFree(host_);
-}
-
 void* HostComm::stage(size_t bytes) {
   if (bytes > cap_) {
-    if (host_) TWTML_HIP_CHECK(hipHostFree(host_));
     cap_ = std::max(bytes, cap_ * 2);
-    TWTML_HIP_CHECK(hipHostMalloc(&host_, cap_, hipHostMallocDefault));
+    host_.alloc(cap_, hipHostMallocDefault);
   }
   return host_;
 }

@@ -23,6 +23,8 @@
 #include <string>
 #include <vector>
 
+#include "owned.h"
+
 namespace twtml {
 
 class Comm {
@@ -117,7 +119,6 @@ class HostComm final : public Comm {
   // from root, -2 all-gather (host holds world * count elements, rank r's at r * count)
   using Fn = std::function<void(void* host, size_t count, ncclDataType_t dt, int op, int root)>;
   HostComm(int rank, int world, Fn fn);
-  ~HostComm() override;
   void allreduce(void* buf, size_t count, ncclDataType_t dt, ncclRedOp_t op, hipStream_t s) override;
   void broadcast(void* buf, size_t count, ncclDataType_t dt, int root, hipStream_t s) override;
   void allgather(const void* send, void* recv, size_t count, ncclDataType_t dt, hipStream_t s) override;
@@ -126,7 +127,7 @@ class HostComm final : public Comm {
  private:
   void* stage(size_t bytes);
   Fn fn_;
-  void* host_ = nullptr;
+  Pinned<void> host_;
   size_t cap_ = 0;
 };
 

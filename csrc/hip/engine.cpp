@@ -1,7 +1,6 @@
 // LREngine implementation; see engine.h.
 #include "engine.h"
 #include "../common/task_pool.h"
-#include "alloc.h"
 #include "trace.h"
 
 #include <algorithm>
@@ -27,10 +26,10 @@ HostBatch::HostBatch(int64_t rows, int64_t text_bytes) : max_rows(rows), max_byt
   const size_t sc = up(sizeof(int64_t) * 5 * size_t(rows));
   const size_t rp = up(sizeof(uint16_t) * size_t(rows) + 16);
   bytes = rp + t + o + r + 2 * sc;
-  TWTML_HIP_CHECK(hipHostMalloc(&base, bytes, hipHostMallocDefault));
+  base.alloc(bytes, hipHostMallocDefault);
   // [row words | text | offsets | flags | scalars | spack]: the row words of
   // n rows end right before the text (pack_rows), so both cross PCIe as one copy
-  char* p = static_cast<char*>(base);
+  char* p = static_cast<char*>(base.get());
   text = reinterpret_cast<uint8_t*>(p + rp);
   rowpack = reinterpret_cast<uint16_t*>(p);
   p += rp;
@@ -242,15 +241,6 @@ void HostBatch::load_utf8(const uint8_t* t, const int64_t* boff, const uint8_t* 
   utf8 = true;
 }
 
-HostBatch::~HostBatch() {
-  if (base) (void)hipHostFree(base);
-}
-
-template <typename T>
-static T* dmalloc(size_t n) {
-  return static_cast<T*>(dev_alloc(n * sizeof(T)));
-}
-
 LREngine::LREngine(int device, const LRConfig& cfg, std::shared_ptr<Comm> comm)
     : device_(device), cfg_(cfg), comm_(std::move(comm)) {
   if (cfg_.num_text_features <= 0) throw std::invalid_argument("numTextFeatures must be > 0");
@@ -278,7 +268,7 @@ LREngine::LREngine(int device, const LRConfig& cfg, std::shared_ptr<Comm> comm)
   // the GD loop outranks the prepare-ahead of the next batch for free CUs
   int lo = 0, hi = 0;
   TWTML_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  TWTML_HIP_CHECK(hipStreamCreateWithPriority(&compute_, hipStreamNonBlocking, hi));
+  compute_ = Stream(hipStreamNonBlocking, hi);
   // TWTML_PREP_CU=k:n[:s] (tuning, off by default): the prep stream may only
   // use CUs i with (i / s) % n < k (measured: no gain, profiles/README.md)
   if (const char* v = std::getenv("TWTML_PREP_CU")) {
@@ -287,34 +277,34 @@ LREngine::LREngine(int device, const LRConfig& cfg, std::shared_ptr<Comm> comm)
       std::vector<uint32_t> mask(size_t((num_cu_ + 31) / 32), 0u);
       for (int i = 0; i < num_cu_; ++i)
         if ((i / st) % n < k) mask[size_t(i / 32)] |= 1u << (i % 32);
-      TWTML_HIP_CHECK(hipExtStreamCreateWithCUMask(&pstream_, uint32_t(mask.size()), mask.data()));
+      pstream_ = Stream(mask);
     }
   }
-  if (!pstream_) TWTML_HIP_CHECK(hipStreamCreateWithPriority(&pstream_, hipStreamNonBlocking, lo));
-  TWTML_HIP_CHECK(hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking));
+  if (!pstream_) pstream_ = Stream(hipStreamNonBlocking, lo);
+  copy_ = Stream(hipStreamNonBlocking);
   raw_.init(cfg_.raw_slots, cfg_.max_rows, text_bytes_for_units(cfg_.max_units));
-  for (auto& e : ev_) TWTML_HIP_CHECK(hipEventCreate(&e));
-  upload_lower_tables(compute_, &lower_page_, &lower_blocks_);
+  for (auto& e : ev_) e = Event(hipEventDefault);
+  upload_lower_tables(compute_, arena_, &lower_page_, &lower_blocks_);
   near_cap_ = tier_near_cap();
   if (const char* v = std::getenv("TWTML_NEAR_CAP"))   // tests / tuning: a smaller LDS tier
     near_cap_ = std::max<int64_t>(64, std::min<int64_t>(near_cap_, std::atoll(v)));
   for (int k = 0; k < (overlap_ ? 2 : 1); ++k) alloc_prepared(pb_[k]);
   const int64_t nw = num_weights();
   sgd_.F = cfg_.num_text_features;
-  sgd_.w64 = dmalloc<double>(size_t(nw));
+  sgd_.w64 = arena_.alloc<double>(size_t(nw));
   TWTML_HIP_CHECK(hipMemset(sgd_.w64, 0, sizeof(double) * size_t(nw)));  // Vectors.zeros
-  sgd_.touched = dmalloc<uint8_t>(size_t(nw));
+  sgd_.touched = arena_.alloc<uint8_t>(size_t(nw));
   TWTML_HIP_CHECK(hipMemset(sgd_.touched, 0, size_t(nw)));
-  sgd_.stats = dmalloc<double>(8);
-  sgd_.stat_i = dmalloc<int64_t>(16);
-  sgd_.stat_part = dmalloc<int64_t>(size_t(kStatBlocks) * 16);
-  sgd_.state = dmalloc<double>(kStateLen);
-  sgd_.loss_hist = dmalloc<double>(size_t(std::max(1, cfg_.num_iterations)) + 2);
-  sgd_.itrec = dmalloc<double>((size_t(std::max(1, cfg_.num_iterations)) + 2) * kRecStride);
-  sgd_.pred_out = dmalloc<float>(size_t(cfg_.max_rows));
-  sgd_.real_out = dmalloc<float>(size_t(cfg_.max_rows));
-  sgd_.nrm = dmalloc<double>(2 * kNormParts);
-  sgd_.wnorm_next = dmalloc<double>(1);
+  sgd_.stats = arena_.alloc<double>(8);
+  sgd_.stat_i = arena_.alloc<int64_t>(16);
+  sgd_.stat_part = arena_.alloc<int64_t>(size_t(kStatBlocks) * 16);
+  sgd_.state = arena_.alloc<double>(kStateLen);
+  sgd_.loss_hist = arena_.alloc<double>(size_t(std::max(1, cfg_.num_iterations)) + 2);
+  sgd_.itrec = arena_.alloc<double>((size_t(std::max(1, cfg_.num_iterations)) + 2) * kRecStride);
+  sgd_.pred_out = arena_.alloc<float>(size_t(cfg_.max_rows));
+  sgd_.real_out = arena_.alloc<float>(size_t(cfg_.max_rows));
+  sgd_.nrm = arena_.alloc<double>(2 * kNormParts);
+  sgd_.wnorm_next = arena_.alloc<double>(1);
   sgd_.world = world_;
   sgd_.rank = comm_ ? comm_->rank() : 0;
   sgd_.tail_len = sgd_tail_len(world_);
@@ -325,32 +315,21 @@ LREngine::LREngine(int device, const LRConfig& cfg, std::shared_ptr<Comm> comm)
   // middle of the stream.  Larger active sets still grow on demand.
   ensure_compact((kNumNumeric + active_set_hint() + kPadSlots + 63) / 64 * 64);
   // the batch's results: written by k_batch_out into mapped host memory
-  TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host_stat_), 16 * sizeof(int64_t),
-                                hipHostMallocMapped | hipHostMallocCoherent));
-  TWTML_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&host_stat_dev_), host_stat_, 0));
-  TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host_out_),
-                                (32 + size_t(std::max(1, cfg_.num_iterations))) * sizeof(double),
-                                hipHostMallocMapped | hipHostMallocCoherent));
-  TWTML_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&host_out_dev_), host_out_, 0));
+  constexpr unsigned kMapped = hipHostMallocMapped | hipHostMallocCoherent;
+  host_stat_.alloc(16 * sizeof(int64_t), kMapped);
+  host_out_.alloc((32 + size_t(std::max(1, cfg_.num_iterations))) * sizeof(double), kMapped);
   // the plot sample: written by k_plot_sample straight into mapped host
   // memory (no copy engine: an 80 KB D2H on the compute stream was measured
   // waiting 25 ms behind other transfers once per process)
-  TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&plot_host_), 2 * sizeof(float) * size_t(cfg_.max_rows),
-                                hipHostMallocMapped | hipHostMallocCoherent));
-  TWTML_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&plot_dev_), plot_host_, 0));
-  TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host_flags_),
-                                (2 + size_t(std::max(1, cfg_.num_iterations))) * sizeof(double),
-                                hipHostMallocMapped | hipHostMallocCoherent));
-  TWTML_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&sgd_.host_flags), host_flags_, 0));
+  plot_host_.alloc(2 * sizeof(float) * size_t(cfg_.max_rows), kMapped);
+  host_flags_.alloc((2 + size_t(std::max(1, cfg_.num_iterations))) * sizeof(double), kMapped);
+  sgd_.host_flags = host_flags_.dev();
   if (dp_) {
-    TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ready_host_), 64, hipHostMallocMapped | hipHostMallocCoherent));
+    ready_host_.alloc(64, kMapped);
     *ready_host_ = 0;
-    int64_t* dev_ready = nullptr;
-    TWTML_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dev_ready), ready_host_, 0));
-    sgd_.ready_word = dev_ready;
-    dnu_ = dmalloc<int64_t>(size_t(world_));
-    TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hnu_), sizeof(int64_t) * size_t(world_),
-                                  hipHostMallocDefault));
+    sgd_.ready_word = ready_host_.dev();
+    dnu_ = arena_.alloc<int64_t>(size_t(world_));
+    hnu_.alloc(sizeof(int64_t) * size_t(world_), hipHostMallocDefault);
   }
   TWTML_HIP_CHECK(hipDeviceSynchronize());
   if (overlap_) worker_ = std::thread([this] { prep_worker(); });
@@ -367,74 +346,53 @@ void LREngine::alloc_prepared(PrepBuf& b) {
   p.cap_rows16 = R16;
   p.cap_chunks = C;
   p.cap_entries = E;
-  p.kept = dmalloc<int64_t>(size_t(R));
-  p.nnz = dmalloc<int32_t>(size_t(R));
-  p.sorted = dmalloc<int32_t>(size_t(R));
-  p.blk = dmalloc<int64_t>(size_t(R / kBlock + 2));
-  p.hist = dmalloc<int64_t>(kLenBuckets + 1);
-  p.clen8 = dmalloc<int32_t>(size_t(C) + 1);
-  p.cfast = dmalloc<uint8_t>(size_t(C) + 1);
-  p.clen8d = dmalloc<int32_t>(size_t(C) + 1);
-  p.cnt = dmalloc<uint16_t>(size_t(E));
-  p.cslot = dmalloc<uint16_t>(size_t(E));
-  p.hot_dense = dmalloc<uint32_t>(size_t(C) * kWave * 4);
-  p.clen8c = dmalloc<int32_t>(size_t(C) + 1);
-  p.hot_slot = dmalloc<int32_t>(kHot);
-  p.hot_of = dmalloc<uint8_t>(kMaxHybridSlots);
-  p.slot_hist = dmalloc<uint32_t>(kMaxHybridSlots);
+  p.kept = b.arena.alloc<int64_t>(size_t(R));
+  p.nnz = b.arena.alloc<int32_t>(size_t(R));
+  p.sorted = b.arena.alloc<int32_t>(size_t(R));
+  p.blk = b.arena.alloc<int64_t>(size_t(R / kBlock + 2));
+  p.hist = b.arena.alloc<int64_t>(kLenBuckets + 1);
+  p.clen8 = b.arena.alloc<int32_t>(size_t(C) + 1);
+  p.cfast = b.arena.alloc<uint8_t>(size_t(C) + 1);
+  p.clen8d = b.arena.alloc<int32_t>(size_t(C) + 1);
+  p.cnt = b.arena.alloc<uint16_t>(size_t(E));
+  p.cslot = b.arena.alloc<uint16_t>(size_t(E));
+  p.hot_dense = b.arena.alloc<uint32_t>(size_t(C) * kWave * 4);
+  p.clen8c = b.arena.alloc<int32_t>(size_t(C) + 1);
+  p.hot_slot = b.arena.alloc<int32_t>(kHot);
+  p.hot_of = b.arena.alloc<uint8_t>(kMaxHybridSlots);
+  p.slot_hist = b.arena.alloc<uint32_t>(kMaxHybridSlots);
   b.slot_hist_cap = kMaxHybridSlots;
-  p.code = dmalloc<uint16_t>(8192);
-  p.cbase = dmalloc<int64_t>(size_t(C) + 1);
-  p.idx = dmalloc<int32_t>(size_t(E));
-  p.slot = dmalloc<uint32_t>(size_t(E));
-  p.y = dmalloc<float>(size_t(R16));
-  p.num = dmalloc<float>(4 * size_t(R16));
-  p.perm = dmalloc<int32_t>(size_t(R16));
-  p.rtext = dmalloc<int64_t>(size_t(R16));
-  p.scan_tmp = dmalloc<int64_t>(size_t(C) / 2048 + 2);   // multi-block scan tiles of 2048
+  p.code = b.arena.alloc<uint16_t>(8192);
+  p.cbase = b.arena.alloc<int64_t>(size_t(C) + 1);
+  p.idx = b.arena.alloc<int32_t>(size_t(E));
+  p.slot = b.arena.alloc<uint32_t>(size_t(E));
+  p.y = b.arena.alloc<float>(size_t(R16));
+  p.num = b.arena.alloc<float>(4 * size_t(R16));
+  p.perm = b.arena.alloc<int32_t>(size_t(R16));
+  p.rtext = b.arena.alloc<int64_t>(size_t(R16));
+  p.scan_tmp = b.arena.alloc<int64_t>(size_t(C) / 2048 + 2);   // multi-block scan tiles of 2048
   // active-feature flags: Java-hash bigrams are < 2^21 whatever F is
   const int64_t F = cfg_.num_text_features;
   int64_t fl = cfg_.hash_kind == 0 ? std::min<int64_t>(F, int64_t(1) << 21) : F;
   fl = (fl + 4095) / 4096 * 4096;
   p.flag_len = fl;
-  p.flags = dmalloc<uint8_t>(size_t(fl));
+  p.flags = b.arena.alloc<uint8_t>(size_t(fl));
   TWTML_HIP_CHECK(hipMemset(p.flags, 0, size_t(fl)));
-  p.uniq = dmalloc<int32_t>(size_t(fl));
-  p.slot_of = dmalloc<int32_t>(size_t(fl));
-  p.ublk = dmalloc<int64_t>(size_t(fl / 4096) + 2);
-  p.counters = dmalloc<int64_t>(8);
-  b.n_global = dmalloc<int64_t>(2 * size_t(world_) + 2);
-  b.bounds = dmalloc<double>(kBoundsLen);
-  TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b.host_counters),
-                                (8 + 2 * size_t(world_)) * sizeof(int64_t), hipHostMallocDefault));
-  TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b.host_norm), 2 * sizeof(int64_t), hipHostMallocDefault));
-  TWTML_HIP_CHECK(hipEventCreate(&b.ev_start));
-  TWTML_HIP_CHECK(hipEventCreate(&b.ev_done));
+  p.uniq = b.arena.alloc<int32_t>(size_t(fl));
+  p.slot_of = b.arena.alloc<int32_t>(size_t(fl));
+  p.ublk = b.arena.alloc<int64_t>(size_t(fl / 4096) + 2);
+  p.counters = b.arena.alloc<int64_t>(8);
+  b.n_global = b.arena.alloc<int64_t>(2 * size_t(world_) + 2);
+  b.bounds = b.arena.alloc<double>(kBoundsLen);
+  b.host_counters.alloc((8 + 2 * size_t(world_)) * sizeof(int64_t), hipHostMallocDefault);
+  b.host_norm.alloc(2 * sizeof(int64_t), hipHostMallocDefault);
+  b.ev_start = Event(hipEventDefault);
+  b.ev_done = Event(hipEventDefault);
   if (dp_) {
-    TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b.host_hdr),
-                                  sizeof(int64_t) * size_t(world_) * (kC1HeaderWords / 2), hipHostMallocDefault));
-    TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b.host_bounds), sizeof(double) * kBoundsLen,
-                                  hipHostMallocDefault));
-    TWTML_HIP_CHECK(hipEventCreateWithFlags(&b.ev_c1, hipEventDisableTiming));
+    b.host_hdr.alloc(sizeof(int64_t) * size_t(world_) * (kC1HeaderWords / 2), hipHostMallocDefault);
+    b.host_bounds.alloc(sizeof(double) * kBoundsLen, hipHostMallocDefault);
+    b.ev_c1 = Event(hipEventDisableTiming);
   }
-}
-
-void LREngine::free_prepared(PrepBuf& b) {
-  DevPrepared& p = b.dp;
-  void* bufs[] = {p.kept, p.nnz, p.sorted, p.blk, p.hist, p.clen8, p.cfast, p.clen8d, p.cnt, p.cslot,
-                  p.hot_dense, p.clen8c, p.hot_slot, p.hot_of, p.slot_hist, p.code, p.cbase, p.idx, p.slot,
-                  p.y, p.num, p.perm, p.rtext, p.scan_tmp, p.flags, p.uniq, p.slot_of, p.ublk, p.counters,
-                  p.fslot, p.fcount, p.fhist, p.fcur, p.fcsc, p.newslot, p.slot_fid, p.tscan,
-                  p.tscan_blk, p.hist_near, p.tparam, b.n_global, b.ugather, b.bounds, b.packet, b.gathered};
-  for (void* x : bufs) if (x) (void)hipFree(x);
-  if (b.host_counters) (void)hipHostFree(b.host_counters);
-  if (b.host_norm) (void)hipHostFree(b.host_norm);
-  if (b.host_hdr) (void)hipHostFree(b.host_hdr);
-  if (b.host_bounds) (void)hipHostFree(b.host_bounds);
-  if (b.ev_c1) (void)hipEventDestroy(b.ev_c1);
-  if (b.ev_start) (void)hipEventDestroy(b.ev_start);
-  if (b.ev_done) (void)hipEventDestroy(b.ev_done);
-  b = PrepBuf{};
 }
 
 // Host side of the early stop: spin (with back-off) on the zero-copy verdict
@@ -464,31 +422,27 @@ void LREngine::ensure_tier(PrepBuf& b, int64_t n_unique, hipStream_t s) {
   DevPrepared& p = b.dp;
   if (!p.fslot) {
     const size_t E = size_t(p.cap_entries);
-    p.fslot = dmalloc<uint32_t>(E);
-    p.fcsc = dmalloc<uint2>(E);
-    p.fcount = dmalloc<int32_t>(size_t(p.cap_chunks) + 1);
-    p.hist_near = dmalloc<uint32_t>(kMaxHybridSlots);
-    p.tparam = dmalloc<int64_t>(4);
+    p.fslot = b.arena.alloc<uint32_t>(E);
+    p.fcsc = b.arena.alloc<uint2>(E);
+    p.fcount = b.arena.alloc<int32_t>(size_t(p.cap_chunks) + 1);
+    p.hist_near = b.arena.alloc<uint32_t>(kMaxHybridSlots);
+    p.tparam = b.arena.alloc<int64_t>(4);
   }
   if (n_unique <= p.cap_tier) return;
   // first sized for the configuration's largest active set (see the
-  // constructor): a regrowth syncs and frees on the prep thread, and hipFree
-  // waits for the whole device -- the batch training meanwhile stalls
+  // constructor), on the prep thread; one sync of `s` for all of them
   TWTML_HIP_CHECK(hipStreamSynchronize(s));
-  void* old[] = {p.newslot, p.slot_fid, p.tscan, p.tscan_blk, p.fhist, p.fcur};
-  for (void* x : old) if (x) (void)hipFree(x);
   const int64_t cap = std::max({n_unique, p.cap_tier * 2, p.cap_tier == 0 ? active_set_hint() : int64_t(0)});
   p.cap_tier = cap;
-  p.newslot = dmalloc<int32_t>(size_t(cap));
-  p.slot_fid = dmalloc<int32_t>(size_t(cap) + kNumNumeric + 2 * kPadSlots);
-  p.tscan = dmalloc<int64_t>(size_t(cap) + 1 + 2048);   // + 4096 u32 count buckets
-  p.tscan_blk = dmalloc<int64_t>(size_t(cap) / 2048 + 4);   // multi-block scan tiles of 2048
-  p.fhist = dmalloc<uint64_t>(size_t(cap) + 1);
-  p.fcur = dmalloc<uint64_t>(size_t(cap) + 1);
+  b.arena.grow(p.newslot, size_t(cap), nullptr);
+  b.arena.grow(p.slot_fid, size_t(cap) + kNumNumeric + 2 * kPadSlots, nullptr);
+  b.arena.grow(p.tscan, size_t(cap) + 1 + 2048, nullptr);   // + 4096 u32 count buckets
+  b.arena.grow(p.tscan_blk, size_t(cap) / 2048 + 4, nullptr);   // multi-block scan tiles of 2048
+  b.arena.grow(p.fhist, size_t(cap) + 1, nullptr);
+  b.arena.grow(p.fcur, size_t(cap) + 1, nullptr);
   if (cap + kNumNumeric + 64 > b.slot_hist_cap) {
-    (void)hipFree(p.slot_hist);
     b.slot_hist_cap = cap + kNumNumeric + 64;
-    p.slot_hist = dmalloc<uint32_t>(size_t(b.slot_hist_cap));
+    b.arena.grow(p.slot_hist, size_t(b.slot_hist_cap), nullptr);
     // stream-ordered: the null stream does not order against the engine's
     // non-blocking streams, so a plain hipMemset could land after the
     // histogram pass that follows on `s`
@@ -507,28 +461,18 @@ int64_t LREngine::active_set_hint() const {
 
 void LREngine::ensure_part(int64_t n) {
   if (n <= part_cap_) return;
-  if (sgd_.part) {
-    TWTML_HIP_CHECK(hipStreamSynchronize(compute_));
-    (void)hipFree(sgd_.part);
-  }
   part_cap_ = std::max<int64_t>(n, part_cap_ * 2);
-  sgd_.part = dmalloc<int64_t>(size_t(part_cap_));
+  arena_.grow(sgd_.part, size_t(part_cap_), compute_);
 }
 
 void LREngine::ensure_compact(int64_t ns) {
   if (ns <= ns_cap_) return;
   int64_t cap = std::max<int64_t>(ns, ns_cap_ * 2);
-  if (sgd_.wc64) {
-    TWTML_HIP_CHECK(hipStreamSynchronize(compute_));
-    (void)hipFree(sgd_.wc64);
-    (void)hipFree(sgd_.wc32);
-    (void)hipFree(sgd_.gacc);
-  }
-  sgd_.wc64 = dmalloc<double>(size_t(cap));
-  sgd_.wc32 = dmalloc<float>(size_t(cap));
+  arena_.grow(sgd_.wc64, size_t(cap), compute_);   // the one sync for all three
+  arena_.grow(sgd_.wc32, size_t(cap), nullptr);
   // packed int64 buffer: near columns (<= cap) | tail | far slots (<= cap)
   const size_t gl = 2 * size_t(cap) + size_t(sgd_tail_len(world_)) + 64;
-  sgd_.gacc = dmalloc<int64_t>(gl);
+  arena_.grow(sgd_.gacc, gl, nullptr);
   // zeroed on the compute stream, ahead of the kernels that accumulate into
   // it (a null-stream hipMemset is unordered against the non-blocking
   // compute stream and could wipe an iteration's far gradients)
@@ -547,39 +491,9 @@ LREngine::~LREngine() {
   // a fault of this engine's last work surfaces here: report it (and keep it
   // for teardown_errors()) instead of leaving it to the next engine's first call
   report_teardown_error("LREngine", device_, hipDeviceSynchronize());
-  raw_.release();
-  for (auto& e : ev_) (void)hipEventDestroy(e);
-  for (auto& b : pb_) free_prepared(b);
-  if (snap_stream_) {
-    (void)hipStreamSynchronize(snap_stream_);
-    (void)hipStreamDestroy(snap_stream_);
-  }
-  if (snap_ev_) (void)hipEventDestroy(snap_ev_);
-  if (snap_src_ev_) (void)hipEventDestroy(snap_src_ev_);
-  for (void* b : {static_cast<void*>(snap_cnt_), static_cast<void*>(snap_off_), static_cast<void*>(snap_idx_),
-                  static_cast<void*>(snap_val_), static_cast<void*>(snap_tidx_), static_cast<void*>(snap_tval_)})
-    if (b) (void)hipFree(b);
-  if (snap_total_) (void)hipHostFree(snap_total_);
-  if (snap_stage_) (void)hipHostFree(snap_stage_);
-  void* bufs[] = {sgd_.gacc, sgd_.rbuf, sgd_.pbuf, sgd_.stat_i, sgd_.stat_part, sgd_.w64, sgd_.touched, sgd_.wc64,
-                  sgd_.wc32,
-                  sgd_.stats, sgd_.state,
-                  sgd_.loss_hist, sgd_.pred_out, sgd_.real_out, sgd_.nrm, sgd_.wnorm_next, sgd_.part, sgd_.itrec, iter_tdbg_, iter_kdbg_,
-                  lower_page_, lower_blocks_};
-  for (void* b : bufs) if (b) (void)hipFree(b);
-  if (host_out_) (void)hipHostFree(host_out_);
-  if (host_stat_) (void)hipHostFree(host_stat_);
-  if (plot_host_) (void)hipHostFree(plot_host_);
-  if (host_flags_) (void)hipHostFree(host_flags_);
-  if (ready_host_) (void)hipHostFree(ready_host_);
-  if (hnu_) (void)hipHostFree(hnu_);
-  if (dnu_) (void)hipFree(dnu_);
-  if (standin_buf_) (void)hipFree(standin_buf_);
-  for (auto e : iter_events_) (void)hipEventDestroy(e);
-  for (auto e : comm_ev_) (void)hipEventDestroy(e);
-  (void)hipStreamDestroy(compute_);
-  (void)hipStreamDestroy(pstream_);
-  (void)hipStreamDestroy(copy_);
+  // the snapshot stream's last copy is done before its buffers go; the
+  // members release everything (streams last, see engine.h)
+  if (snap_stream_) (void)hipStreamSynchronize(snap_stream_);
 }
 
 void LREngine::submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, const uint8_t* ext_text,
@@ -653,9 +567,9 @@ void LREngine::prepare_local(PrepBuf& pb, int slot, int64_t now_ms, hipStream_t 
       launch_tier_hist(prep, nU, num_cu_, s);
     }
     if (nU > pb.pkt_cap || !pb.packet) {
-      if (pb.packet) (void)hipFree(pb.packet);
       pb.pkt_cap = std::max<int64_t>(std::max<int64_t>(2 * nU, 4096), pb.pkt_cap);
-      pb.packet = dmalloc<int32_t>(size_t(c1_packet_words(pb.pkt_cap)));
+      // the one regrowth without a stream sync (hipFree itself waits for the device)
+      pb.arena.grow(pb.packet, size_t(c1_packet_words(pb.pkt_cap)), nullptr);
     }
     launch_pack_c1(prep, pb.bounds, pb.packet, nU, s);
     // back to zero for the hybrid remap's own histogram (k_prep_init zeroed the rest)
@@ -695,21 +609,17 @@ void LREngine::issue_c1(PrepBuf& pb, int64_t max_u) {
   hipStream_t s = compute_;
   const int64_t pw = c1_packet_words(max_u);
   if (max_u > pb.pkt_cap) {   // another rank's active set is larger than this packet holds (rare)
-    int32_t* np = dmalloc<int32_t>(size_t(pw));
+    int32_t* np = pb.arena.alloc<int32_t>(size_t(pw));   // keeps its contents: copy, then free the old one
     TWTML_HIP_CHECK(hipMemcpyAsync(np, pb.packet, sizeof(int32_t) * size_t(c1_packet_words(pb.nu_local)),
                                    hipMemcpyDeviceToDevice, s));
     TWTML_HIP_CHECK(hipStreamSynchronize(s));
-    (void)hipFree(pb.packet);
+    pb.arena.free(pb.packet);
     pb.packet = np;
     pb.pkt_cap = max_u;
   }
   if (max_u > pb.gath_cap || !pb.gathered) {
-    if (pb.gathered) {
-      TWTML_HIP_CHECK(hipStreamSynchronize(s));
-      (void)hipFree(pb.gathered);
-    }
     pb.gath_cap = std::max<int64_t>(max_u + max_u / 4 + 1024, pb.gath_cap);
-    pb.gathered = dmalloc<int32_t>(size_t(world_) * size_t(c1_packet_words(pb.gath_cap)));
+    pb.arena.grow(pb.gathered, size_t(world_) * size_t(c1_packet_words(pb.gath_cap)), s);
   }
   if (max_u > pb.nu_local)   // pad this rank's pairs to the largest rank's: id -1
     TWTML_HIP_CHECK(hipMemsetAsync(pb.packet + c1_packet_words(pb.nu_local), 0xFF,
@@ -719,7 +629,7 @@ void LREngine::issue_c1(PrepBuf& pb, int64_t max_u) {
   std::lock_guard<std::mutex> lk(mu_);
   pb.c1_maxu = max_u;
   pb.c1 = 2;
-  __atomic_store_n(ready_host_, int64_t(0), __ATOMIC_RELEASE);
+  __atomic_store_n(ready_host_.get(), int64_t(0), __ATOMIC_RELEASE);
   cv_.notify_all();
 }
 
@@ -878,11 +788,11 @@ BatchResult LREngine::train(PrepBuf& pb, bool want_pred, int64_t plot_points) {
   sgd_.bounds = pb.bounds;
   sgd_.far_off = pb.nl + sgd_.tail_len;
   if (tiered) {
-    if (!sgd_.rbuf) sgd_.rbuf = dmalloc<float>(size_t(prep.cap_rows16));
+    if (!sgd_.rbuf) sgd_.rbuf = arena_.alloc<float>(size_t(prep.cap_rows16));
     sgd_.fcsc = prep.fcsc;
     sgd_.far_n = prep.tparam + 2;
   }
-  if (!sgd_.pbuf) sgd_.pbuf = dmalloc<float>(size_t(prep.cap_rows16));
+  if (!sgd_.pbuf) sgd_.pbuf = arena_.alloc<float>(size_t(prep.cap_rows16));
   launch_batch_init(sgd_, double(n_glob), cfg_.num_iterations + 2, s);  // state[5] = m (global kept rows)
   if (norm_age_ < 0 || norm_age_ >= kNormRefresh) {
     launch_norm2(sgd_.w64, num_weights(), &sgd_.state[4], sgd_, s);
@@ -925,23 +835,19 @@ BatchResult LREngine::train(PrepBuf& pb, bool want_pred, int64_t plot_points) {
     // match.
     const int depth = std::max(2, cfg_.early_exit_depth);
     const int iters = cfg_.num_iterations;
-    std::fill(host_flags_, host_flags_ + iters + 2, -1.0);   // -1: verdict not published yet
+    std::fill(host_flags_.get(), host_flags_ + iters + 2, -1.0);   // -1: verdict not published yet
     // single GPU with partial rows: the update kernel reduces them itself
     const bool fused = !dp_ && sgd_.nparts > 0;
     const bool itime = std::getenv("TWTML_ITER_TIMING") != nullptr;
-    if (itime && !iter_tdbg_) iter_tdbg_ = dmalloc<uint64_t>(4096 + size_t(iters + 2) * 32);
+    if (itime && !iter_tdbg_) iter_tdbg_ = arena_.alloc<uint64_t>(4096 + size_t(iters + 2) * 32);
     const size_t kd_words = size_t(iters + 2) * kKdbgKinds * kKdbgWgs * 2;
-    if (itime && !iter_kdbg_) iter_kdbg_ = dmalloc<uint64_t>(kd_words);
+    if (itime && !iter_kdbg_) iter_kdbg_ = arena_.alloc<uint64_t>(kd_words);
     sgd_.tdbg = itime ? iter_tdbg_ : nullptr;
     sgd_.kdbg = itime ? iter_kdbg_ : nullptr;
     if (itime) TWTML_HIP_CHECK(hipMemsetAsync(iter_tdbg_, 0, sizeof(uint64_t) * (4096 + size_t(iters + 2) * 32), s));
     if (itime) TWTML_HIP_CHECK(hipMemsetAsync(iter_kdbg_, 0, sizeof(uint64_t) * kd_words, s));
     if (comm_timing_ && comm_ev_.size() < size_t(2 * iters)) {
-      for (size_t q = comm_ev_.size(); q < size_t(2 * iters); ++q) {
-        hipEvent_t e;
-        TWTML_HIP_CHECK(hipEventCreate(&e));
-        comm_ev_.push_back(e);
-      }
+      for (size_t q = comm_ev_.size(); q < size_t(2 * iters); ++q) comm_ev_.emplace_back(hipEventDefault);
     }
     for (int i = 1; i <= iters; ++i) {
       if (i > depth) {
@@ -979,12 +885,8 @@ BatchResult LREngine::train(PrepBuf& pb, bool want_pred, int64_t plot_points) {
         if (standin_wgs_ > 0) {   // DP cost model: the CU footprint of a multi-rank all-reduce
           const int64_t nw = sgd_.far_off + n_far;
           if (nw > standin_cap_) {
-            if (standin_buf_) {
-              TWTML_HIP_CHECK(hipStreamSynchronize(s));
-              (void)hipFree(standin_buf_);
-            }
             standin_cap_ = nw + nw / 4;
-            standin_buf_ = dmalloc<int64_t>(size_t(standin_cap_));
+            arena_.grow(standin_buf_, size_t(standin_cap_), s);
           }
           launch_rccl_standin(sgd_.gacc, standin_buf_, nw, standin_wgs_, sgd_.kdbg, i, s);
         }
@@ -1011,7 +913,7 @@ BatchResult LREngine::train(PrepBuf& pb, bool want_pred, int64_t plot_points) {
     comm_->allreduce(sgd_.stat_i, size_t(kStatI), ncclInt64, ncclSum, s);
     comm_->allreduce(sgd_.stats, 6, ncclFloat64, ncclSum, s);
   }
-  launch_batch_out(sgd_, host_out_dev_, host_stat_dev_, cfg_.num_iterations + 1, s);
+  launch_batch_out(sgd_, host_out_.dev(), host_stat_.dev(), cfg_.num_iterations + 1, s);
   TWTML_HIP_CHECK(hipEventRecord(ev_[4], s));
   // the plot's (pred, real) pairs of this rank's kept rows: all of them, or
   // plot_points evenly spaced ones sampled on the device, written by the
@@ -1019,7 +921,7 @@ BatchResult LREngine::train(PrepBuf& pb, bool want_pred, int64_t plot_points) {
   size_t P = 0;
   if (want_pred && res.n_kept > 0) {
     P = size_t(plot_points > 0 ? std::min<int64_t>(plot_points, res.n_kept) : res.n_kept);
-    launch_plot_sample(sgd_.pred_out, sgd_.real_out, res.n_kept, int64_t(P), plot_dev_, s);
+    launch_plot_sample(sgd_.pred_out, sgd_.real_out, res.n_kept, int64_t(P), plot_host_.dev(), s);
   }
   TWTML_HIP_CHECK(hipEventRecord(ev_[3], s));
   TWTML_HIP_CHECK(hipStreamSynchronize(s));
@@ -1159,7 +1061,7 @@ void LREngine::prep_worker() {
         // all-reduce) and wait for the training thread's all-gather
         lk.lock();
         b.c1 = 1;
-        __atomic_store_n(ready_host_, b.nu_local + 1, __ATOMIC_RELEASE);
+        __atomic_store_n(ready_host_.get(), b.nu_local + 1, __ATOMIC_RELEASE);
         cv_.notify_all();
         cv_.wait(lk, [&] { return stop_ || b.c1 == 2 || b.c1 == -2; });
         if (stop_) return;
@@ -1396,23 +1298,22 @@ void LREngine::snapshot_begin() {
   if (n >= (int64_t(1) << 31)) throw std::runtime_error("snapshot: more than 2^31 weights");
   if (!snap_idx_) {   // once: F+4 pairs worst case (1.2 GB at F = 1e8, of 288 GB)
     const int64_t nb = snapshot_chunks(n);
-    snap_cnt_ = static_cast<uint32_t*>(dev_alloc(sizeof(uint32_t) * size_t(nb)));
-    snap_off_ = static_cast<int64_t*>(dev_alloc(sizeof(int64_t) * size_t(nb + 1)));
-    snap_idx_ = static_cast<int32_t*>(dev_alloc(sizeof(int32_t) * size_t(n)));
-    snap_val_ = static_cast<double*>(dev_alloc(sizeof(double) * size_t(n)));
-    snap_tidx_ = static_cast<int32_t*>(dev_alloc(sizeof(int32_t) * size_t(n)));
-    snap_tval_ = static_cast<double*>(dev_alloc(sizeof(double) * size_t(n)));
-    TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&snap_total_), sizeof(int64_t), hipHostMallocMapped));
-    TWTML_HIP_CHECK(hipHostMalloc(&snap_stage_, size_t(kSnapStage), hipHostMallocDefault));
+    snap_cnt_ = arena_.alloc<uint32_t>(size_t(nb));
+    snap_off_ = arena_.alloc<int64_t>(size_t(nb + 1));
+    snap_idx_ = arena_.alloc<int32_t>(size_t(n));
+    snap_val_ = arena_.alloc<double>(size_t(n));
+    snap_tidx_ = arena_.alloc<int32_t>(size_t(n));
+    snap_tval_ = arena_.alloc<double>(size_t(n));
+    snap_total_.alloc(sizeof(int64_t), hipHostMallocMapped);
+    snap_stage_.alloc(size_t(kSnapStage), hipHostMallocDefault);
     int lo = 0, hi = 0;
     TWTML_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    TWTML_HIP_CHECK(hipStreamCreateWithPriority(&snap_stream_, hipStreamNonBlocking, lo));
-    TWTML_HIP_CHECK(hipEventCreateWithFlags(&snap_ev_, hipEventDisableTiming));
-    TWTML_HIP_CHECK(hipEventCreateWithFlags(&snap_src_ev_, hipEventDisableTiming));
+    snap_stream_ = Stream(hipStreamNonBlocking, lo);
+    snap_ev_ = Event(hipEventDisableTiming);
+    snap_src_ev_ = Event(hipEventDisableTiming);
   }
   *snap_total_ = -1;
-  int64_t* dtot = nullptr;
-  TWTML_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dtot), snap_total_, 0));
+  int64_t* dtot = snap_total_.dev();
   // The master weights change only in k_scatter_w at the end of a batch, so
   // the compaction runs on its own low-priority stream behind the last
   // batch and overlaps the next batch's prep and GD loop; that batch's
@@ -1444,7 +1345,7 @@ int64_t LREngine::snapshot_wait() {
     if (!snap_pending_) throw std::runtime_error("snapshot_wait: no snapshot was begun");
   }
   TWTML_HIP_CHECK(hipEventSynchronize(snap_ev_));
-  const int64_t nnz = __atomic_load_n(snap_total_, __ATOMIC_ACQUIRE);
+  const int64_t nnz = __atomic_load_n(snap_total_.get(), __ATOMIC_ACQUIRE);
   if (nnz < 0 || nnz > num_weights()) throw std::runtime_error("snapshot: bad non-zero count");
   return nnz;
 }

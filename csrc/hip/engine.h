@@ -31,6 +31,7 @@
 #include "comm.h"
 #include "common.h"
 #include "kernels.h"
+#include "owned.h"
 #include "raw_slots.h"
 
 namespace twtml {
@@ -68,7 +69,7 @@ struct LRConfig {
 inline size_t rowpack_prefix(int64_t n) { return (sizeof(uint16_t) * size_t(n) + 15) & ~size_t(15); }
 
 struct HostBatch {
-  void* base = nullptr;
+  Pinned<void> base;
   size_t bytes = 0;
   uint8_t* text = nullptr;
   int64_t* offsets = nullptr;
@@ -95,7 +96,6 @@ struct HostBatch {
   int64_t range_hits = 0, range_misses = 0;   // pack_scalars with a range hint: one pass / fell back
   int64_t max_rows = 0, max_bytes = 0;
   HostBatch(int64_t rows, int64_t text_bytes);
-  ~HostBatch();
   // Encode scalars[:, :n] (or src [5][n]) into spack (one thread per column).
   // range: optional [lo 0..4 | hi 0..4] column bounds the receiver recorded
   // while sealing the batch: the encoding is chosen from them and the packing
@@ -163,29 +163,33 @@ struct BatchResult {
 // One prepared micro-batch: filtered, featurized, compacted and laid out for
 // the GD kernels.  Two of them, so batch t+1 is prepared on the prep stream
 // (by the engine's prep thread) while batch t trains on the compute stream.
+// A buffer's device memory (its arena) is touched by the prep thread
+// (ensure_tier, the packet) and by the training thread (issue_c1), never by
+// both at once: the c1 / state protocol under LREngine::mu_ hands it over.
 struct PrepBuf {
+  DevArena arena;                     // owns every device buffer below (dp's included)
   DevPrepared dp{};
   int64_t slot_hist_cap = 0;
   int64_t* n_global = nullptr;        // device [2 world + 2]: per-rank kept rows | active-set sizes
   int32_t* ugather = nullptr;         // DP active-set union: all-gathered id lists
   int64_t ugather_cap = 0;
-  int64_t* host_counters = nullptr;   // pinned [8 + 2 world]: counters | per-rank kept | per-rank active
+  Pinned<int64_t> host_counters;      // pinned [8 + 2 world]: counters | per-rank kept | per-rank active
   // DP prep packet (dp_prep.hip) and the all-gathered packets of every rank
   int32_t* packet = nullptr;          // device [c1_packet_words(pkt_cap)]
   int64_t pkt_cap = 0;
   int32_t* gathered = nullptr;        // device [world * c1_packet_words(gath_cap)]
   int64_t gath_cap = 0;
-  int64_t* host_hdr = nullptr;        // pinned [world * kC1HeaderWords / 2] gathered headers
-  double* host_bounds = nullptr;      // pinned [kBoundsLen]
-  hipEvent_t ev_c1 = nullptr;         // compute stream, after the all-gather
+  Pinned<int64_t> host_hdr;           // pinned [world * kC1HeaderWords / 2] gathered headers
+  Pinned<double> host_bounds;         // pinned [kBoundsLen]
+  Event ev_c1;                        // compute stream, after the all-gather
   int64_t nu_local = 0;               // this rank's active ids (packet pairs)
   int64_t c1_maxu = 0;                // pairs per rank in the all-gather
   int c1 = 0;                         // guarded by mu_: 0 -, 1 packet ready, 2 all-gather issued, -1 failed,
                                       // -2 a peer failed (no all-gather)
-  int64_t* host_norm = nullptr;       // pinned [2] rows lowered / narrowed on the device
+  Pinned<int64_t> host_norm;          // pinned [2] rows lowered / narrowed on the device
   double* bounds = nullptr;           // device [kBoundsLen] batch bounds of the fixed-point scales
                                       // (DP: the max over ranks)
-  hipEvent_t ev_start = nullptr, ev_done = nullptr;
+  Event ev_start, ev_done;
   // guarded by LREngine::mu_
   int state = 0;                      // 0 free, 1 being prepared, 2 prepared
   int slot = -1;
@@ -283,7 +287,6 @@ class LREngine {
 
  private:
   void alloc_prepared(PrepBuf& b);
-  void free_prepared(PrepBuf& b);
   void ensure_compact(int64_t ns);
   void ensure_part(int64_t n);
   int64_t active_set_hint() const;
@@ -312,15 +315,19 @@ class LREngine {
   int world_ = 1;
   bool dp_ = false;                 // DP path: world > 1, or forced with a world-1 communicator
   bool comm_timing_ = false;
-  std::vector<hipEvent_t> comm_ev_; // comm_timing: [2 iters] around each gradient all-reduce
-  hipStream_t compute_ = nullptr, pstream_ = nullptr, copy_ = nullptr;
+  // Members are destroyed in reverse order: the streams outlive every
+  // buffer, event and raw slot declared below them.
+  Stream compute_, pstream_, copy_;
+  Stream snap_stream_;              // weight snapshots; created by the first snapshot_begin
+  DevArena arena_;                  // the engine's own device buffers (training thread)
+  std::vector<Event> comm_ev_;      // comm_timing: [2 iters] around each gradient all-reduce
   RawSlots raw_;
   PrepBuf pb_[2];
   int last_buf_ = -1;               // buffer of the last trained batch (debug_*)
   bool overlap_ = true;
-  int64_t* ready_host_ = nullptr;   // DP: pinned mapped ready word (next packet's pairs + 1; 0: none)
+  Pinned<int64_t> ready_host_;      // DP: pinned mapped ready word (next packet's pairs + 1; 0: none)
   int64_t* dnu_ = nullptr;          // DP: device [world] active-set sizes (in-line all-gather sizing)
-  int64_t* hnu_ = nullptr;          // pinned [world]
+  Pinned<int64_t> hnu_;             // pinned [world]
   // prepare-ahead: submitted slots in order, the prep thread's job (a pb_ index)
   std::mutex mu_;
   std::condition_variable cv_;
@@ -349,19 +356,15 @@ class LREngine {
   uint64_t* iter_tdbg_ = nullptr;
   uint8_t* lower_page_ = nullptr;
   uint16_t* lower_blocks_ = nullptr;
-  double* host_out_ = nullptr;        // mapped pinned [16 + iters]: stats, state, loss history
-  int64_t* host_stat_ = nullptr;      // mapped pinned [16]: exact batch moments (stat_i)
-  double* host_out_dev_ = nullptr;    // device view of host_out_ (k_batch_out)
-  int64_t* host_stat_dev_ = nullptr;  // device view of host_stat_
+  Pinned<double> host_out_;           // mapped pinned [16 + iters]: stats, state, loss history (k_batch_out)
+  Pinned<int64_t> host_stat_;         // mapped pinned [16]: exact batch moments (stat_i)
   uint64_t* iter_kdbg_ = nullptr;     // TWTML_ITER_TIMING: per-workgroup GD kernel stamps
   int standin_wgs_ = 0;               // DP: TWTML_RCCL_STANDIN workgroups after each gradient all-reduce
   int64_t* standin_buf_ = nullptr;    // ... their destination buffer
   int64_t standin_cap_ = 0;
-  float* plot_host_ = nullptr;        // mapped pinned [2 max_rows]: sampled (pred, real) pairs
-  float* plot_dev_ = nullptr;         // ... its device address (k_plot_sample writes it)
-  double* host_flags_ = nullptr;      // pinned [iters + 1] convergence flag per iteration
-  std::vector<hipEvent_t> iter_events_;
-  hipEvent_t ev_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  Pinned<float> plot_host_;           // mapped pinned [2 max_rows]: sampled (pred, real) pairs (k_plot_sample)
+  Pinned<double> host_flags_;         // mapped pinned [iters + 1] convergence flag per iteration
+  Event ev_[5];
   int num_cu_ = 256;
   // weight snapshot (snapshot.hip); allocated on the first snapshot_begin
   std::mutex snap_mu_;
@@ -372,13 +375,12 @@ class LREngine {
   double* snap_val_ = nullptr;
   int32_t* snap_tidx_ = nullptr;      // scratch pairs of the one-pass compaction (snapshot.hip)
   double* snap_tval_ = nullptr;
-  int64_t* snap_total_ = nullptr;     // pinned mapped
-  void* snap_stage_ = nullptr;        // pinned staging, kSnapStage bytes
+  Pinned<int64_t> snap_total_;        // pinned mapped
+  Pinned<void> snap_stage_;           // pinned staging, kSnapStage bytes
   std::vector<int32_t> snap_hidx_;    // snapshot_host
   std::vector<double> snap_hval_;
-  hipStream_t snap_stream_ = nullptr;
-  hipEvent_t snap_ev_ = nullptr;      // snapshot kernels done (snap_stream_)
-  hipEvent_t snap_src_ev_ = nullptr;  // the batch the snapshot is taken after (compute_)
+  Event snap_ev_;                     // snapshot kernels done (snap_stream_)
+  Event snap_src_ev_;                 // the batch the snapshot is taken after (compute_)
   bool snap_guard_ = false;           // the next scatter into w64 must wait for snap_ev_
   static constexpr int64_t kSnapStage = 32ll << 20;
 };

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "narrow_text.h"
+#include "owned.h"
 #include "text_stage.h"
 
 namespace twtml {
@@ -1414,9 +1415,9 @@ void launch_dedup(const DevPrepared& p, int64_t ns, int64_t pad_base, int64_t n_
 }
 
 // ---------------------------------------------------------------------------
-void upload_lower_tables(hipStream_t s, uint8_t** d_page, uint16_t** d_blocks) {
-  TWTML_HIP_CHECK(hipMalloc(d_page, 256));
-  TWTML_HIP_CHECK(hipMalloc(d_blocks, sizeof(uint16_t) * 256 * uni::kLowerNumBlocks));
+void upload_lower_tables(hipStream_t s, DevArena& arena, uint8_t** d_page, uint16_t** d_blocks) {
+  *d_page = arena.alloc<uint8_t>(256);
+  *d_blocks = arena.alloc<uint16_t>(256 * size_t(uni::kLowerNumBlocks));
   TWTML_HIP_CHECK(hipMemcpyAsync(*d_page, uni::kLowerPage, 256, hipMemcpyHostToDevice, s));
   TWTML_HIP_CHECK(hipMemcpyAsync(*d_blocks, uni::kLowerBlocks,
                                  sizeof(uint16_t) * 256 * uni::kLowerNumBlocks,

@@ -17,6 +17,8 @@
 
 namespace twtml {
 
+class DevArena;   // owned.h
+
 // ---------------------------------------------------------------------------
 // Raw batch on the device (one ingest slot).
 // Raw batch in the wire format (csrc/host/wire.h).
@@ -84,8 +86,9 @@ struct DevCaseTables {
   const uint32_t* bmp_class = nullptr;     // [4096] the class of every BMP code point, 2 bits each
   int32_t n_supp = 0, n_ranges = 0;
 };
-void upload_case_tables(DevCaseTables* ct);
-void free_case_tables(DevCaseTables* ct);
+// allocated from / returned to the caller's arena
+void upload_case_tables(DevArena& arena, DevCaseTables* ct);
+void free_case_tables(DevArena& arena, DevCaseTables* ct);
 // Special-row full case mapping (+ narrowing of Latin-1 rows of UTF-16
 // batches when `narrow`), see rows.hip.  Reads rows at [cur_s, cur_e),
 // writes every row's extents to out_s / out_e (may alias cur_*) and clears
@@ -199,7 +202,8 @@ struct FeaturizeParams {
   int64_t c_lo = 0, c_hi = INT64_MAX;
 };
 
-void upload_lower_tables(hipStream_t s, uint8_t** d_page, uint16_t** d_blocks);
+// lower-casing tables, allocated from the caller's arena
+void upload_lower_tables(hipStream_t s, DevArena& arena, uint8_t** d_page, uint16_t** d_blocks);
 
 // zero counters, length histogram, n_global[0..ng) and the hybrid slot
 // histogram (before launch_filter_sort)

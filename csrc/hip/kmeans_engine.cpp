@@ -1,6 +1,5 @@
 // KMEngine: the streaming k-means micro-batch pipeline (see kmeans.hip).
 #include "kmeans_engine.h"
-#include "alloc.h"
 #include "trace.h"
 
 #include <pybind11/numpy.h>
@@ -18,11 +17,6 @@
 namespace py = pybind11;
 
 namespace twtml {
-
-template <typename T>
-static T* km_alloc(size_t n) {
-  return static_cast<T*>(dev_alloc(n * sizeof(T)));
-}
 
 static int pad_dim(int d) {
   for (int p : {2, 4, 8, 16, 32, 64, 128})
@@ -42,46 +36,43 @@ KMEngine::KMEngine(int device, const KMConfig& cfg, std::shared_ptr<Comm> comm)
   dist_ = comm_ && (comm_->world() > 1 || cfg_.force_dp != 0 || (fdp && fdp[0] == '1'));
   dp_ = pad_dim(d_);
   TWTML_HIP_CHECK(hipSetDevice(device_));
-  TWTML_HIP_CHECK(hipStreamCreateWithFlags(&compute_, hipStreamNonBlocking));
-  TWTML_HIP_CHECK(hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking));
+  compute_ = Stream(hipStreamNonBlocking);
+  copy_ = Stream(hipStreamNonBlocking);
   raw_.init(cfg_.raw_slots, cfg_.max_rows, text_bytes_for_units(cfg_.max_units));
   const int64_t R = cfg_.max_rows;
   prep_.cap_rows = R;
-  prep_.kept = km_alloc<int64_t>(size_t(R));
-  prep_.nnz = km_alloc<int32_t>(size_t(R));
-  prep_.blk = km_alloc<int64_t>(size_t(R / kBlock + 2));
-  prep_.hist = km_alloc<int64_t>(kLenBuckets + 1);
-  prep_.counters = km_alloc<int64_t>(8);
-  X_ = km_alloc<float>(size_t(R) * size_t(dp_));
+  prep_.kept = arena_.alloc<int64_t>(size_t(R));
+  prep_.nnz = arena_.alloc<int32_t>(size_t(R));
+  prep_.blk = arena_.alloc<int64_t>(size_t(R / kBlock + 2));
+  prep_.hist = arena_.alloc<int64_t>(kLenBuckets + 1);
+  prep_.counters = arena_.alloc<int64_t>(8);
+  X_ = arena_.alloc<float>(size_t(R) * size_t(dp_));
   const size_t k = size_t(cfg_.k), d = size_t(d_);
-  centers_ = km_alloc<double>(k * d);
-  weights_ = km_alloc<double>(k);
-  sums_ = km_alloc<double>(k * d + k);
-  sums_i_ = km_alloc<int64_t>(k * d + k);
-  qmom_ = km_alloc<int64_t>(d + 1 + 4 * d);   // [d] column max | n | [d][4] sums of q and limbs
-  fac64_ = km_alloc<double>(size_t(dp_));
-  fac32_ = km_alloc<float>(size_t(dp_));
-  blend_ = km_alloc<double>(2 * k);
-  c32_ = km_alloc<float>(k * size_t(dp_));
-  cnorm_ = km_alloc<float>(k);
-  labels_ = km_alloc<int32_t>(size_t(R));
-  order_ = km_alloc<int32_t>(size_t(R));
-  refine_ = km_alloc<int32_t>(6 * size_t(R));
-  frag_ = km_alloc<uint16_t>(km_frag_elems(cfg_.k, dp_));
-  cnp_ = km_alloc<float>(size_t((cfg_.k + 31) / 32) * 32);
-  lhist_ = km_alloc<int64_t>(k + 1);
+  centers_ = arena_.alloc<double>(k * d);
+  weights_ = arena_.alloc<double>(k);
+  sums_ = arena_.alloc<double>(k * d + k);
+  sums_i_ = arena_.alloc<int64_t>(k * d + k);
+  qmom_ = arena_.alloc<int64_t>(d + 1 + 4 * d);   // [d] column max | n | [d][4] sums of q and limbs
+  fac64_ = arena_.alloc<double>(size_t(dp_));
+  fac32_ = arena_.alloc<float>(size_t(dp_));
+  blend_ = arena_.alloc<double>(2 * k);
+  c32_ = arena_.alloc<float>(k * size_t(dp_));
+  cnorm_ = arena_.alloc<float>(k);
+  labels_ = arena_.alloc<int32_t>(size_t(R));
+  order_ = arena_.alloc<int32_t>(size_t(R));
+  refine_ = arena_.alloc<int32_t>(6 * size_t(R));
+  frag_ = arena_.alloc<uint16_t>(km_frag_elems(cfg_.k, dp_));
+  cnp_ = arena_.alloc<float>(size_t((cfg_.k + 31) / 32) * 32);
+  lhist_ = arena_.alloc<int64_t>(k + 1);
   // on the compute stream: the null stream does not order against it
   TWTML_HIP_CHECK(hipMemsetAsync(centers_, 0, sizeof(double) * k * d, compute_));
   TWTML_HIP_CHECK(hipMemsetAsync(weights_, 0, sizeof(double) * k, compute_));
-  upload_lower_tables(compute_, &lower_page_, &lower_blocks_);
-  TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host_out_), sizeof(double) * (4 + d),
-                                hipHostMallocDefault));
-  TWTML_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host_q_), sizeof(int64_t) * (d + 1 + 4 * d),
-                                hipHostMallocDefault));
-  TWTML_HIP_CHECK(hipHostMalloc(&host_fac_, sizeof(double) * size_t(dp_) + sizeof(float) * size_t(dp_),
-                                hipHostMallocDefault));
-  TWTML_HIP_CHECK(hipEventCreate(&ev0_));
-  TWTML_HIP_CHECK(hipEventCreate(&ev1_));
+  upload_lower_tables(compute_, arena_, &lower_page_, &lower_blocks_);
+  host_out_.alloc(sizeof(double) * (4 + d), hipHostMallocDefault);
+  host_q_.alloc(sizeof(int64_t) * (d + 1 + 4 * d), hipHostMallocDefault);
+  host_fac_.alloc(sizeof(double) * size_t(dp_) + sizeof(float) * size_t(dp_), hipHostMallocDefault);
+  ev0_ = Event(hipEventDefault);
+  ev1_ = Event(hipEventDefault);
   launch_km_centers32(centers_, cfg_.k, d_, dp_, c32_, cnorm_, compute_);
   TWTML_HIP_CHECK(hipStreamSynchronize(compute_));
 }
@@ -91,18 +82,7 @@ KMEngine::~KMEngine() {
   // a fault of this engine's last work surfaces here: report it (and keep it
   // for teardown_errors()) instead of leaving it to the next engine's first call
   report_teardown_error("KMEngine", device_, hipDeviceSynchronize());
-  raw_.release();
-  void* bufs[] = {prep_.kept, prep_.nnz, prep_.blk, prep_.hist, prep_.counters, X_, centers_,
-                  weights_, sums_, sums_i_, qmom_, c32_, cnorm_, labels_, order_, refine_, frag_, cnp_, lhist_, fac64_, fac32_, blend_,
-                  lower_page_, lower_blocks_};
-  for (void* b : bufs) if (b) (void)hipFree(b);
-  if (host_out_) (void)hipHostFree(host_out_);
-  if (host_q_) (void)hipHostFree(host_q_);
-  if (host_fac_) (void)hipHostFree(host_fac_);
-  (void)hipEventDestroy(ev0_);
-  (void)hipEventDestroy(ev1_);
-  (void)hipStreamDestroy(compute_);
-  (void)hipStreamDestroy(copy_);
+  // the members release everything (streams last, see kmeans_engine.h)
 }
 
 void KMEngine::submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, const uint8_t* ext_text) {
@@ -152,7 +132,7 @@ KMResult KMEngine::process(int slot, bool want_labels) {
   // std_j = sqrt(M2_j / (n - 1)) (n < 2 -> 0); factor_j = std_j != 0 ? 1 / std_j : 0
   // (StandardScalerModel.transform), M2 = (n sum q^2 - (sum q)^2) / n in
   // 128-bit integers; scale == 0 -> factor 1
-  double* f64 = static_cast<double*>(host_fac_);
+  double* f64 = static_cast<double*>(host_fac_.get());
   float* f32 = reinterpret_cast<float*>(f64 + dp_);
   if (cfg_.scale) res.std.assign(size_t(d), 0.0);
   for (int j = 0; j < dp_; ++j) {

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "engine.h"
 #include "kernels.h"
+#include "owned.h"
 
 namespace twtml {
 
@@ -65,15 +66,18 @@ class KMEngine {
   int d_, dp_;
   bool dist_ = false;   // DP collectives: world > 1, or forced with a world-1 communicator
   std::shared_ptr<Comm> comm_;
-  hipStream_t compute_ = nullptr, copy_ = nullptr;
+  // Members are destroyed in reverse order: the streams outlive every
+  // buffer, event and raw slot declared below them.
+  Stream compute_, copy_;
+  DevArena arena_;                     // owns every device buffer below (prep_'s included)
   RawSlots raw_;
   DevPrepared prep_{};
   float* X_ = nullptr;
   double *centers_ = nullptr, *weights_ = nullptr, *sums_ = nullptr;
   int64_t* sums_i_ = nullptr;          // [k d + k] per-cluster integer sums of q, counts (all-reduced)
   int64_t* qmom_ = nullptr;            // [d] column max | n | [d][4] integer moments (all-reduced)
-  int64_t* host_q_ = nullptr;          // pinned copy of qmom_
-  void* host_fac_ = nullptr;           // pinned [dp] fp64 + [dp] fp32 factors (H2D staging)
+  Pinned<int64_t> host_q_;             // pinned copy of qmom_
+  Pinned<void> host_fac_;              // pinned [dp] fp64 + [dp] fp32 factors (H2D staging)
   float *c32_ = nullptr, *cnorm_ = nullptr, *fac32_ = nullptr;
   double *fac64_ = nullptr, *blend_ = nullptr;
   int32_t *labels_ = nullptr, *order_ = nullptr, *refine_ = nullptr;
@@ -82,8 +86,8 @@ class KMEngine {
   int64_t* lhist_ = nullptr;
   uint8_t* lower_page_ = nullptr;
   uint16_t* lower_blocks_ = nullptr;
-  double* host_out_ = nullptr;
-  hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
+  Pinned<double> host_out_;
+  Event ev0_, ev1_;
 };
 
 void bind_kmeans(pybind11::module_& m);

@@ -1,5 +1,4 @@
 #include "raw_slots.h"
-#include "alloc.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -8,11 +7,6 @@
 #include "engine.h"
 
 namespace twtml {
-
-template <typename T>
-static T* slot_alloc(size_t n) {
-  return static_cast<T*>(dev_alloc(n * sizeof(T)));
-}
 
 int RawSlots::check(int slot) const {
   if (slot < 0 || slot >= int(slots_.size())) throw std::invalid_argument("slot must be in [0, raw slots)");
@@ -23,27 +17,27 @@ void RawSlots::init(int n_slots, int64_t max_rows, int64_t max_bytes) {
   if (max_rows < 0 || max_bytes < 0) throw std::invalid_argument("RawSlots: negative capacity");
   if (n_slots < 2 || n_slots > kMaxRawSlots) throw std::invalid_argument("RawSlots: 2 .. 32 slots");
   release();
-  slots_.assign(size_t(n_slots), Slot{});
+  slots_ = std::vector<Slot>(size_t(n_slots));
   max_rows_ = max_rows;
   max_bytes_ = max_bytes;
   for (auto& s : slots_) {
     // wire bytes + cesu rows expanded behind them (UTF-16: at most twice the
     // wire bytes of those rows); slack: featurize over-reads <= 80 B
     const size_t pre = (rowpack_prefix(max_rows) + 255) & ~size_t(255);
-    s.text_base = slot_alloc<uint8_t>(pre + 5 * size_t(max_bytes) + 256);
-    s.nstats = slot_alloc<int64_t>(4);
-    s.special = slot_alloc<int32_t>(size_t(max_rows) + 1);
+    s.text_base = s.arena.alloc<uint8_t>(pre + 5 * size_t(max_bytes) + 256);
+    s.nstats = s.arena.alloc<int64_t>(4);
+    s.special = s.arena.alloc<int32_t>(size_t(max_rows) + 1);
     s.text = s.text_base + pre;
-    s.offsets = slot_alloc<int64_t>(size_t(max_rows) + 1);
-    s.flags = slot_alloc<uint8_t>(size_t(max_rows));
-    s.scalars = slot_alloc<int64_t>(5 * size_t(max_rows));
-    s.tsum = slot_alloc<int64_t>(size_t(max_rows) / 8192 + 2);
-    s.rstart = slot_alloc<int64_t>(size_t(max_rows) + 1);
-    s.rend = slot_alloc<int64_t>(size_t(max_rows) + 1);
-    TWTML_HIP_CHECK(hipEventCreateWithFlags(&s.h2d_done, hipEventDisableTiming));
-    TWTML_HIP_CHECK(hipEventCreateWithFlags(&s.consumed, hipEventDisableTiming));
+    s.offsets = s.arena.alloc<int64_t>(size_t(max_rows) + 1);
+    s.flags = s.arena.alloc<uint8_t>(size_t(max_rows));
+    s.scalars = s.arena.alloc<int64_t>(5 * size_t(max_rows));
+    s.tsum = s.arena.alloc<int64_t>(size_t(max_rows) / 8192 + 2);
+    s.rstart = s.arena.alloc<int64_t>(size_t(max_rows) + 1);
+    s.rend = s.arena.alloc<int64_t>(size_t(max_rows) + 1);
+    s.h2d_done = Event(hipEventDisableTiming);
+    s.consumed = Event(hipEventDisableTiming);
   }
-  upload_case_tables(&case_);
+  upload_case_tables(arena_, &case_);
 }
 
 std::vector<std::array<double, 4>> RawSlots::h2d_timeline() {
@@ -71,18 +65,17 @@ bool RawSlots::timing_on() {
 
 void RawSlots::h2d_window_mark(hipStream_t copy) {
   if (!timing_on()) return;
-  hipEvent_t e = nullptr;
-  TWTML_HIP_CHECK(hipEventCreate(&e));
+  Event e(hipEventDefault);
   TWTML_HIP_CHECK(hipEventRecord(e, copy));
   std::lock_guard<std::mutex> lk(tl_mu_);
-  win_.push_back(e);
+  win_.push_back(std::move(e));
 }
 
 std::vector<double> RawSlots::h2d_window() {
   std::lock_guard<std::mutex> lk(tl_mu_);
   std::vector<double> out;
   if (tl_.empty()) return out;
-  for (hipEvent_t e : win_) {
+  for (const Event& e : win_) {
     TWTML_HIP_CHECK(hipEventSynchronize(e));
     float t = 0.f;
     TWTML_HIP_CHECK(hipEventElapsedTime(&t, tl_.front().q, e));
@@ -92,30 +85,10 @@ std::vector<double> RawSlots::h2d_window() {
 }
 
 void RawSlots::release() {
-  for (hipEvent_t e : win_) (void)hipEventDestroy(e);
   win_.clear();
-  for (H2DMark& m : tl_) {
-    if (m.q) (void)hipEventDestroy(m.q);
-    if (m.a) (void)hipEventDestroy(m.a);
-    if (m.b) (void)hipEventDestroy(m.b);
-  }
   tl_.clear();
-  for (auto& s : slots_) {
-    if (s.text_base) (void)hipFree(s.text_base);
-    if (s.offsets) (void)hipFree(s.offsets);
-    if (s.flags) (void)hipFree(s.flags);
-    if (s.scalars) (void)hipFree(s.scalars);
-    if (s.tsum) (void)hipFree(s.tsum);
-    if (s.rstart) (void)hipFree(s.rstart);
-    if (s.rend) (void)hipFree(s.rend);
-    if (s.nstats) (void)hipFree(s.nstats);
-    if (s.special) (void)hipFree(s.special);
-    if (s.h2d_done) (void)hipEventDestroy(s.h2d_done);
-    if (s.consumed) (void)hipEventDestroy(s.consumed);
-    s = Slot{};
-  }
   slots_.clear();
-  free_case_tables(&case_);
+  free_case_tables(arena_, &case_);
 }
 
 void RawSlots::submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, hipStream_t copy,
@@ -133,9 +106,9 @@ void RawSlots::submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, h
   const bool timed = timing_on();
   H2DMark mark;
   if (timed) {   // queued: before the slot wait
-    TWTML_HIP_CHECK(hipEventCreate(&mark.q));
-    TWTML_HIP_CHECK(hipEventCreate(&mark.a));
-    TWTML_HIP_CHECK(hipEventCreate(&mark.b));
+    mark.q = Event(hipEventDefault);
+    mark.a = Event(hipEventDefault);
+    mark.b = Event(hipEventDefault);
     TWTML_HIP_CHECK(hipEventRecord(mark.q, copy));
   }
   // wait until the compute stream has finished reading this slot
@@ -161,7 +134,7 @@ void RawSlots::submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, h
     // them are one contiguous copy; it must fit both the host block's spack
     // region (its tail) and the slot's 5 x 8 B per row
     const int64_t sbytes = hb.soff[scalar_cols];
-    const uint8_t* hend = static_cast<const uint8_t*>(hb.base) + hb.bytes;
+    const uint8_t* hend = static_cast<const uint8_t*>(hb.base.get()) + hb.bytes;
     if (sbytes < 0 || sbytes > 5 * int64_t(sizeof(int64_t)) * n || hb.spack + sbytes > hend)
       throw std::logic_error("RawSlots::submit: packed scalar bytes out of range (" + std::to_string(sbytes) +
                              " for " + std::to_string(n) + " rows)");
@@ -190,7 +163,7 @@ void RawSlots::submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, h
     TWTML_HIP_CHECK(hipEventRecord(mark.b, copy));
     mark.bytes = moved;
     std::lock_guard<std::mutex> lk(tl_mu_);
-    tl_.push_back(mark);
+    tl_.push_back(std::move(mark));
   }
   for (int c = 0; c < kScalarCols; ++c) {
     s.soff[c] = hb.soff[c];

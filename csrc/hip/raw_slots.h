@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "owned.h"
 
 namespace twtml {
 
@@ -38,7 +39,6 @@ class RawSlots {
   RawSlots() = default;
   RawSlots(const RawSlots&) = delete;
   RawSlots& operator=(const RawSlots&) = delete;
-  ~RawSlots() { release(); }
 
   void init(int n_slots, int64_t max_rows, int64_t max_bytes);
   int count() const { return int(slots_.size()); }
@@ -83,6 +83,7 @@ class RawSlots {
   int check(int slot) const;
   bool timing_on();   // TWTML_H2D_TIMING, read once
   struct Slot {
+    DevArena arena;                   // owns the slot's device buffers
     uint8_t* text_base = nullptr;     // [row words prefix | text] (one H2D copy)
     uint8_t* text = nullptr;
     int64_t* offsets = nullptr;
@@ -100,20 +101,21 @@ class RawSlots {
     int64_t sbase[kScalarCols] = {};
     uint8_t sw[kScalarCols] = {};
     int64_t n = 0, bytes = 0;
-    hipEvent_t h2d_done = nullptr, consumed = nullptr;
+    Event h2d_done, consumed;
     bool used = false;
   };
   std::vector<Slot> slots_;
   int64_t max_rows_ = 0, max_bytes_ = 0;
   std::atomic<int64_t> h2d_bytes_{0};
   struct H2DMark {
-    hipEvent_t q = nullptr, a = nullptr, b = nullptr;
+    Event q, a, b;
     int64_t bytes = 0;
   };
   std::mutex tl_mu_;
   std::vector<H2DMark> tl_;
-  std::vector<hipEvent_t> win_;
+  std::vector<Event> win_;
   int tl_on_ = -1;   // TWTML_H2D_TIMING, read once
+  DevArena arena_;   // the case tables
   DevCaseTables case_{};
 };
 

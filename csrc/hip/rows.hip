@@ -28,6 +28,7 @@
 #include "../common/unicode_tables.h"
 #include "common.h"
 #include "kernels.h"
+#include "owned.h"
 
 namespace twtml {
 
@@ -331,15 +332,12 @@ static int host_case_class(uint32_t cp) {
   return 0;
 }
 
-void upload_case_tables(DevCaseTables* ct) {
-  uint32_t* sl = nullptr;
-  uint32_t* cr = nullptr;
-  uint32_t* bc = nullptr;
+void upload_case_tables(DevArena& arena, DevCaseTables* ct) {
   std::vector<uint32_t> bmp(4096, 0u);
   for (uint32_t cp = 0; cp < 0x10000u; ++cp) bmp[cp >> 4] |= uint32_t(host_case_class(cp)) << (2 * (cp & 15u));
-  TWTML_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&sl), sizeof(uni::kSuppLower)));
-  TWTML_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cr), sizeof(uni::kCaseRanges)));
-  TWTML_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&bc), bmp.size() * sizeof(uint32_t)));
+  uint32_t* sl = arena.alloc<uint32_t>(sizeof(uni::kSuppLower) / sizeof(uint32_t));
+  uint32_t* cr = arena.alloc<uint32_t>(sizeof(uni::kCaseRanges) / sizeof(uint32_t));
+  uint32_t* bc = arena.alloc<uint32_t>(bmp.size());
   TWTML_HIP_CHECK(hipMemcpy(sl, uni::kSuppLower, sizeof(uni::kSuppLower), hipMemcpyHostToDevice));
   TWTML_HIP_CHECK(hipMemcpy(cr, uni::kCaseRanges, sizeof(uni::kCaseRanges), hipMemcpyHostToDevice));
   TWTML_HIP_CHECK(hipMemcpy(bc, bmp.data(), bmp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -351,10 +349,10 @@ void upload_case_tables(DevCaseTables* ct) {
   ct->n_ranges = uni::kNumCaseRanges;
 }
 
-void free_case_tables(DevCaseTables* ct) {
-  if (ct->supp_lower) (void)hipFree(const_cast<uint32_t*>(ct->supp_lower));
-  if (ct->case_ranges) (void)hipFree(const_cast<uint32_t*>(ct->case_ranges));
-  if (ct->bmp_class) (void)hipFree(const_cast<uint32_t*>(ct->bmp_class));
+void free_case_tables(DevArena& arena, DevCaseTables* ct) {
+  arena.free(ct->supp_lower);
+  arena.free(ct->case_ranges);
+  arena.free(ct->bmp_class);
   *ct = DevCaseTables{};
 }
 

@@ -147,3 +147,71 @@ def test_back_to_back_engines_deep_prefetch_async_checkpoint(hip_module, tmp_pat
         assert not left, _who_holds(left)               # the pool's registrations ended with it
     # three different streams: three different models
     assert not np.array_equal(weights[0], weights[1])
+
+
+def _engine_cycle(hip_module, base):
+    """Construct / train / snapshot / delete one LR and one k-means engine;
+    returns the live device bytes while both exist."""
+    from twitter_stream_ml_amd.ops.kmeans_engine import DeviceKMeans, KMDeviceConfig
+    from twitter_stream_ml_amd.ops.lr_engine import DeviceLinearRegression, LRDeviceConfig
+    from twitter_stream_ml_amd.sources.synthetic import SynthConfig, generate_batch
+    rows = 4096
+    lr = DeviceLinearRegression(LRDeviceConfig(num_text_features=1_000_000, max_rows=rows,
+                                               max_units=rows * 300), device=0)
+    # two shapes: the second one's partial-sum buffer outgrows the first's (ensure_part)
+    for profile, n, seed in (("bench", 300, 11), ("wide", 4000, 12)):
+        r = lr.train_batch(generate_batch(SynthConfig.profile(profile, seed=seed), 0, n, batch_time_ms=NOW))
+        assert r["tiered"] and r["n_kept"] > 0     # the lazily allocated tier buffers exist
+    lr.snapshot_begin()                            # ... and the snapshot buffers and stream
+    size, idx, val = lr.snapshot_fetch()
+    assert size == lr.num_weights and len(idx) == len(val) > 0
+    km = DeviceKMeans(KMDeviceConfig(k=8, text_dims=14, max_rows=rows, max_units=rows * 300), device=0)
+    km.update_raw(generate_batch(SynthConfig.profile("bench", seed=13), 0, 300, batch_time_ms=NOW))
+    held = hip_module.device_bytes_live()
+    assert held > base
+    del lr, km, r, idx, val
+    gc.collect()
+    return held
+
+
+def test_live_device_bytes_return_to_baseline(hip_module, monkeypatch):
+    """Every device buffer an engine allocates -- at construction, lazily at
+    its first tiered batch / snapshot, or by a regrowth -- is released with
+    it: the live-byte counter is back at its baseline exactly (one forgotten
+    8-byte buffer fails this), twice in a row."""
+    monkeypatch.setenv("TWTML_FORCE_TIERED", "1")
+    gc.collect()
+    base = hip_module.device_bytes_live()
+    for _ in range(2):
+        _engine_cycle(hip_module, base)
+        assert hip_module.device_bytes_live() == base
+        assert list(hip_module.teardown_errors()) == []
+
+
+def test_failed_construction_releases_what_it_took(hip_module):
+    """A constructor that throws half-way frees what it had allocated.  The
+    flags buffer of a murmur3 engine has F bytes: with F beyond the device's
+    memory its hipMalloc is refused (an out-of-memory error code on the host;
+    nothing is launched) after the raw slots and ~30 prepared buffers exist."""
+    import torch
+    from twitter_stream_ml_amd.ops.lr_engine import DeviceLinearRegression, LRDeviceConfig
+    from twitter_stream_ml_amd.sources.synthetic import SynthConfig, generate_batch
+    F = 1 << 42
+    total = torch.cuda.mem_get_info(0)[1]
+    if F <= total:
+        pytest.skip("the device holds a 4 TiB buffer")
+    assert F > total
+    gc.collect()
+    base = hip_module.device_bytes_live()
+    cfg = LRDeviceConfig(num_text_features=F, hash="murmur3", max_rows=4096, max_units=4096 * 300)
+    with pytest.raises(RuntimeError):
+        hip_module.LREngine(0, cfg.as_dict(), None)
+    assert hip_module.device_bytes_live() == base
+    assert list(hip_module.teardown_errors()) == []
+    lr = DeviceLinearRegression(LRDeviceConfig(num_text_features=1000, max_rows=4096, max_units=4096 * 300),
+                                device=0)
+    r = lr.train_batch(generate_batch(SynthConfig.profile("bench", seed=14), 0, 300, batch_time_ms=NOW))
+    assert r["n_kept"] > 0 and r["iterations"] > 0 and not r["diverged"]
+    del lr, r
+    gc.collect()
+    assert hip_module.device_bytes_live() == base
