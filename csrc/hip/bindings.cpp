@@ -1,4 +1,5 @@
 // pybind11 bindings of the MI355X engine (_twtml_hip).
+#include <cstring>
 #include <ctime>
 #include <hip/hip_runtime.h>
 #include <pybind11/numpy.h>
@@ -336,12 +337,40 @@ PYBIND11_MODULE(_twtml_hip, m) {
            py::arg("device"), py::arg("config"), py::arg("comm") = nullptr)
       .def("submit",
            [](LREngine& e, const HostBatch& hb, int64_t n, int64_t bytes, int slot, uintptr_t ext_text,
-              int64_t now_ms) {
+              int64_t now_ms, bool train) {
              py::gil_scoped_release nogil;
-             e.submit(hb, n, bytes, slot, reinterpret_cast<const uint8_t*>(ext_text), now_ms);
+             e.submit(hb, n, bytes, slot, reinterpret_cast<const uint8_t*>(ext_text), now_ms, train);
            },
            py::arg("host_batch"), py::arg("n"), py::arg("bytes"), py::arg("slot"), py::arg("ext_text") = 0,
-           py::arg("now_ms") = 0)
+           py::arg("now_ms") = 0, py::arg("train") = true)
+      .def("score",
+           [](LREngine& e, int slot, int64_t now_ms, bool apply_filter) {
+             ScoreResult r;
+             {
+               py::gil_scoped_release nogil;
+               r = e.score(slot, now_ms, apply_filter);
+             }
+             // copies owned by the caller (the engine's pinned buffer is reused)
+             py::array_t<double> pred(r.n_scored);
+             py::array_t<int64_t> rows(r.n_scored);
+             if (r.n_scored > 0) {
+               std::memcpy(pred.mutable_data(), r.pred, sizeof(double) * size_t(r.n_scored));
+               int64_t* pr = rows.mutable_data();
+               if (r.rows) std::memcpy(pr, r.rows, sizeof(int64_t) * size_t(r.n_scored));
+               else for (int64_t i = 0; i < r.n_scored; ++i) pr[i] = i;
+             }
+             py::dict d;
+             d["n_raw"] = r.n_raw;
+             d["n_scored"] = r.n_scored;
+             d["rows"] = rows;
+             d["pred"] = pred;
+             d["score_ms"] = r.score_ms;
+             d["wall_ms"] = r.wall_ms;
+             return d;
+           },
+           py::arg("slot"), py::arg("now_ms"), py::arg("apply_filter") = false,
+           "inference only: fp64 predictions of the batch in `slot` (submitted with train=False) under the "
+           "current weights; rows = raw row ids (ascending), pred in that order")
       .def("process",
            [](LREngine& e, int slot, int64_t now_ms, bool want_pred, int64_t plot_points) {
              BatchResult r;

@@ -497,13 +497,96 @@ LREngine::~LREngine() {
 }
 
 void LREngine::submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, const uint8_t* ext_text,
-                      int64_t now_ms) {
+                      int64_t now_ms, bool train) {
   TraceRange tr("twtml.lr.submit_h2d");
   TWTML_HIP_CHECK(hipSetDevice(device_));
   std::lock_guard<std::mutex> lk(mu_);
+  // a scoring batch must not land in a slot that a queued or prepared
+  // training batch still owns
+  if (!train && training_owns_locked(slot))
+    throw std::logic_error("submit(train=false): the slot holds a batch queued or prepared for training");
   raw_.submit(hb, n, bytes, slot, copy_, kScalarCols, ext_text);
+  if (!train) return;   // score() only: never in the prepare-ahead queue
   submitted_.push_back({slot, now_ms});
   cv_.notify_all();
+}
+
+// ---------------------------------------------------------------------------
+// Inference-only scoring (score.hip) on the compute stream.
+// ---------------------------------------------------------------------------
+// Caller holds mu_: `slot` is in the prepare-ahead queue or a prepared buffer.
+bool LREngine::training_owns_locked(int slot) const {
+  for (const auto& q : submitted_)
+    if (q.first == slot) return true;
+  for (const auto& b : pb_)
+    if (b.state != 0 && b.slot == slot) return true;
+  return false;
+}
+
+void LREngine::ensure_score() {
+  if (score_out_) return;
+  DevPrepared& p = score_dp_;
+  const int64_t R = cfg_.max_rows;
+  const int64_t C = (R + kRowsPerChunk - 1) / kRowsPerChunk;
+  p.cap_rows = R;
+  p.cap_rows16 = C * kRowsPerChunk;
+  p.cap_chunks = C;
+  p.kept = score_arena_.alloc<int64_t>(size_t(R));
+  p.nnz = score_arena_.alloc<int32_t>(size_t(R));
+  p.sorted = score_arena_.alloc<int32_t>(size_t(R));
+  p.blk = score_arena_.alloc<int64_t>(size_t(R / kBlock + 2));
+  p.hist = score_arena_.alloc<int64_t>(kLenBuckets + 1);
+  p.clen8 = score_arena_.alloc<int32_t>(size_t(C) + 1);
+  p.cfast = score_arena_.alloc<uint8_t>(size_t(C) + 1);
+  p.cbase = score_arena_.alloc<int64_t>(size_t(C) + 1);
+  p.scan_tmp = score_arena_.alloc<int64_t>(size_t(C) / 2048 + 2);
+  score_host_.alloc(sizeof(int64_t) * (8 + 2 * size_t(R)), hipHostMallocDefault);
+  score_ev_[0] = Event(hipEventDefault);
+  score_ev_[1] = Event(hipEventDefault);
+  // counters first: one D2H brings them and the results
+  score_out_ = score_arena_.alloc<int64_t>(8 + 2 * size_t(R));
+  p.counters = score_out_;
+}
+
+ScoreResult LREngine::score(int slot, int64_t now_ms, bool apply_filter) {
+  TraceRange tr("twtml.lr.score");
+  TWTML_HIP_CHECK(hipSetDevice(device_));
+  const auto t_in = std::chrono::steady_clock::now();
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (training_owns_locked(slot))
+      throw std::logic_error("score(): the slot holds a batch queued or prepared for training");
+  }
+  ScoreResult res;
+  res.n_raw = raw_.rows(slot);
+  if (res.n_raw == 0) return res;
+  ensure_score();
+  hipStream_t s = compute_;
+  const DevRawBatch b = raw_.acquire(slot, s);
+  const int64_t n = b.n;
+  FeaturizeParams fp{cfg_.num_text_features, cfg_.hash_kind, apply_filter ? cfg_.require_retweet : 0,
+                     apply_filter ? cfg_.range_filter : 0, cfg_.begin, cfg_.end, now_ms};
+  double* pred = reinterpret_cast<double*>(score_out_ + 8);
+  int64_t* rows = apply_filter ? score_out_ + 8 + n : nullptr;
+  TWTML_HIP_CHECK(hipEventRecord(score_ev_[0], s));
+  launch_score_init(score_dp_, s);
+  launch_filter_sort(b, score_dp_, fp, s);
+  launch_chunk_layout(b, score_dp_, s);
+  launch_score(b, score_dp_, fp, lower_page_, lower_blocks_, sgd_.w64, pred, rows, s);
+  TWTML_HIP_CHECK(hipEventRecord(score_ev_[1], s));
+  raw_.release_slot(slot, s);   // the raw slot may be overwritten now
+  const size_t words = 8 + size_t(apply_filter ? 2 * n : n);
+  TWTML_HIP_CHECK(hipMemcpyAsync(score_host_.get(), score_out_, sizeof(int64_t) * words, hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipStreamSynchronize(s));
+  const int64_t* h = score_host_.get();
+  res.n_scored = h[0];
+  if (res.n_scored < 0 || res.n_scored > n || (!apply_filter && res.n_scored != n))
+    throw std::runtime_error("score(): kept-row count out of range");
+  res.pred = reinterpret_cast<const double*>(h + 8);
+  res.rows = apply_filter ? h + 8 + n : nullptr;
+  TWTML_HIP_CHECK(hipEventElapsedTime(&res.score_ms, score_ev_[0], score_ev_[1]));
+  res.wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+  return res;
 }
 
 // ---------------------------------------------------------------------------

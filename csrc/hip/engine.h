@@ -160,6 +160,16 @@ struct BatchResult {
   float phases[7] = {0, 0, 0, 0, 0, 0, 0};   // [6]: the tail's result copies alone
 };
 
+// score(): the scored rows of one raw batch.  rows / pred point into the
+// engine's pinned result buffer and stay valid until the next score() call.
+struct ScoreResult {
+  int64_t n_raw = 0, n_scored = 0;
+  const int64_t* rows = nullptr;   // [n_scored] raw row ids, ascending; null: every row (0 .. n_raw - 1)
+  const double* pred = nullptr;    // [n_scored] fp64 predictions in that order
+  float score_ms = 0.f;            // device time of the filter / sort / layout / scoring kernels (events)
+  float wall_ms = 0.f;             // score() on the host, end to end
+};
+
 // One prepared micro-batch: filtered, featurized, compacted and laid out for
 // the GD kernels.  Two of them, so batch t+1 is prepared on the prep stream
 // (by the engine's prep thread) while batch t trains on the compute stream.
@@ -218,14 +228,27 @@ class LREngine {
 
   // Async H2D of rows [0, n) of a pinned host batch into device slot `slot`.
   // now_ms: the batch's time (featurizeNumbers), used if it is prepared ahead.
+  // train = false: a batch for score() only -- it never enters the
+  // prepare-ahead queue, so the prep thread does not pick it up.
   void submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, const uint8_t* ext_text = nullptr,
-              int64_t now_ms = 0);
+              int64_t now_ms = 0, bool train = true);
   // Train on the batch in `slot` (blocks until done); stats use w before
   // training.  The next submitted slot is then prepared ahead (prep thread,
   // prep stream) while this one trains.
   // plot_points > 0: pred / real hold that many evenly spaced kept rows
   // (sampled on the device), else all of them.
   BatchResult process(int slot, int64_t now_ms, bool want_pred, int64_t plot_points = 0);
+  // Inference only: fp64 predictions of the batch in `slot` (submitted with
+  // train = false) under the current master weights, i.e. after the last
+  // processed batch (blocks until done).  apply_filter: score the rows the
+  // training filter keeps, else every raw row.  Decode and lower-casing are
+  // those of training (the raw slot is acquired the same way); the sum is
+  // score.hip's.  Reads the weights and nothing else of the model: no
+  // prepared buffer, no training state and no pending snapshot is touched, and
+  // no collective is issued (a DP rank may score between any two process()
+  // calls, on its own).  Scratch is allocated by the first call.
+  // score() and process() must be called from the same thread.
+  ScoreResult score(int slot, int64_t now_ms, bool apply_filter);
   // Forget a submitted batch that will not be processed (one GPU only): the
   // slot may be submitted again afterwards (ops/ingest.py SlotPipeline).
   void discard(int slot);
@@ -287,6 +310,8 @@ class LREngine {
 
  private:
   void alloc_prepared(PrepBuf& b);
+  void ensure_score();
+  bool training_owns_locked(int slot) const;
   void ensure_compact(int64_t ns);
   void ensure_part(int64_t n);
   int64_t active_set_hint() const;
@@ -366,6 +391,15 @@ class LREngine {
   Pinned<double> host_flags_;         // mapped pinned [iters + 1] convergence flag per iteration
   Event ev_[5];
   int num_cu_ = 256;
+  // score(): filter / sort / chunk arrays only (no entry-sized buffers), the
+  // device results [8 counters | pred | rows] and their pinned host copy;
+  // allocated by the first score() (not part of lazy_bytes(): sizing covers
+  // training)
+  DevArena score_arena_;
+  DevPrepared score_dp_{};
+  int64_t* score_out_ = nullptr;      // device [8 + 2 max_rows]
+  Pinned<int64_t> score_host_;        // pinned  [8 + 2 max_rows]
+  Event score_ev_[2];
   // weight snapshot (snapshot.hip); allocated on the first snapshot_begin
   std::mutex snap_mu_;
   bool snap_pending_ = false;

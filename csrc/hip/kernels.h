@@ -238,6 +238,18 @@ constexpr int kMaxHybridSlots = 16384;
 void launch_remap_hybrid(const DevPrepared& p, int64_t entries, int64_t ns, int64_t pad_base, int num_cu,
                          const DevRawBatch& b, const FeaturizeParams& fp, bool from_text, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// Inference-only scoring (score.hip): fp64 predictions of the kept rows from
+// the master weights, no entry-sized buffers.  `p` is a scoring-only
+// DevPrepared: kept, nnz, sorted, blk, hist, clen8, cfast, cbase, scan_tmp and
+// counters, everything else null.  Order: launch_score_init,
+// launch_filter_sort, launch_chunk_layout, launch_score.
+void launch_score_init(const DevPrepared& p, hipStream_t s);
+// pred[k] (and rows[k] = raw row id, if rows) of kept row k, in kept (=
+// ascending raw row) order
+void launch_score(const DevRawBatch& b, const DevPrepared& p, const FeaturizeParams& fp, const uint8_t* lower_page,
+                  const uint16_t* lower_blocks, const double* w64, double* pred, int64_t* rows, hipStream_t s);
+
 // Exclusive int64 scan (in place safe); tsum: ceil(n / 2048) + 2 scratch.
 void launch_scan_excl(const int64_t* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum, hipStream_t s,
                       int64_t* out2 = nullptr);

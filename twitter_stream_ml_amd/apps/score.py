@@ -1,0 +1,142 @@
+"""twtml-score: score a tweet stream with a trained model, without training.
+
+Loads an MLlib ``Saveable`` LinearRegressionModel directory -- what the
+LinearRegression driver's ``--checkpoint`` writes -- and scores every
+micro-batch of ``--source synthetic|replay:FILE|twitter`` with it:
+``engine.predict_batch(raw)``, the unfiltered fp64 predictions ``x . w`` of
+every tweet in record order (on ``rocm[N]`` one pass of ``csrc/hip/score.hip``
+per batch, on ``local[N]`` the fp64 CPU engine).  The model is never updated.
+
+``--model DIR``       the model directory; its weight count must be
+                      ``numTextFeatures + 4`` (``-f`` / ``--hash`` as trained)
+``--predictOut DIR``  per batch ``pred_<seq>.npy`` (float64), ``rows_<seq>.npy``
+                      (int64 raw row ids) and one line of ``predictions.jsonl``
+                      (batch time, count, mean / min / max prediction, ms)
+``--numBatches N``    stop after N batches
+
+With more than one rank (``rocm[N>1]``, one process per GPU) every rank
+scores its own shard of the stream and writes its own files, suffixed
+``_r<rank>``; scoring needs no collective.
+"""
+from __future__ import annotations
+
+import json
+import logging
+import os
+import sys
+import time
+from typing import List, Optional
+
+import numpy as np
+
+from ..config.arguments import ConfArguments
+from ..config.hocon import load_java_opts
+from ..models.linear_regression import LinearRegressionModel
+from ..models.mllib_helper import MllibHelper
+from ..runtime.streaming import StreamingContext
+from ..sources import make_source
+from ..utils.logging import setup_logging
+from ._common import exit_on_sigterm
+from .linear_regression import build_engine
+
+__all__ = ["main", "ScoreJob"]
+
+log = logging.getLogger("com.giorgioinf.twtml.spark.Score")
+APP_NAME = "twitter-stream-ml-score"
+
+
+class ScoreJob:
+    """Per-batch logic of the scoring driver."""
+
+    def __init__(self, engine, out_dir: str = "", rank: int = 0, world: int = 1):
+        self.engine = engine
+        self.out_dir = out_dir
+        self.suffix = f"_r{rank}" if world > 1 else ""
+        self.batches = 0
+        self.scored = 0
+        self._jsonl = None
+        if out_dir:
+            os.makedirs(out_dir, exist_ok=True)
+            self._jsonl = open(os.path.join(out_dir, f"predictions{self.suffix}.jsonl"), "a", encoding="utf-8")
+
+    def on_batch(self, rdd, time_ms: int) -> None:
+        raw = rdd.raw
+        t0 = time.perf_counter()
+        res = self.engine.predict_batch(raw, apply_filter=False)
+        ms = (time.perf_counter() - t0) * 1e3
+        pred = np.asarray(res["pred"], np.float64)
+        seq = self.batches
+        self.batches += 1
+        self.scored += int(res["n_scored"])
+        rec = {"seq": seq, "batch_time_ms": int(time_ms), "count": int(res["n_scored"]),
+               "mean": float(pred.mean()) if pred.size else None,
+               "min": float(pred.min()) if pred.size else None,
+               "max": float(pred.max()) if pred.size else None,
+               "ms": round(ms, 3), "score_ms": round(float(res.get("score_ms", 0.0)), 3)}
+        log.debug("batch %d: %d tweets scored in %.3f ms", seq, rec["count"], ms)
+        if self.out_dir:
+            np.save(os.path.join(self.out_dir, f"pred_{seq}{self.suffix}.npy"), pred)
+            np.save(os.path.join(self.out_dir, f"rows_{seq}{self.suffix}.npy"), np.asarray(res["rows"], np.int64))
+            self._jsonl.write(json.dumps(rec) + "\n")
+            self._jsonl.flush()
+
+    def close(self) -> None:
+        if self._jsonl is not None:
+            self._jsonl.close()
+            self._jsonl = None
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    setup_logging()
+    exit_on_sigterm()
+    from ..runtime.clock import streaming_clock
+    args = load_java_opts(list(sys.argv[1:] if argv is None else argv))
+    conf = ConfArguments().setAppName(APP_NAME).parse(args)
+    if not conf.model:
+        print("twtml-score: --model <MLlib model directory> is required", file=sys.stderr)
+        return 2
+    try:
+        w = LinearRegressionModel.load(conf.model).weights
+    except Exception as e:   # noqa: BLE001 -- any unreadable model is the same usage error
+        print(f"twtml-score: cannot load the model at {conf.model}: {e}", file=sys.stderr)
+        return 2
+    want = conf.effectiveNumTextFeatures + 4
+    if w.shape[0] != want:
+        print(f"twtml-score: the model at {conf.model} has {w.shape[0]} weights, but numTextFeatures + 4 = {want} "
+              f"(give the -f / --numTextFeatures the model was trained with)", file=sys.stderr)
+        return 2
+
+    spec = conf.master_spec()
+    # one process per GPU under the launcher; no process group: scoring has no collective
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    MllibHelper.reset(conf)
+    # every rank scores alone: an engine without a communicator, on its GPU
+    dev = (spec.devices[rank] if spec.devices else rank) if spec.is_gpu else None
+    engine = build_engine(conf, 0, 1, device=dev)
+    engine.set_weights(w)
+    log.info("scoring with %d weights from %s", w.shape[0], conf.model)
+
+    cap = getattr(engine, "cfg", None)
+    ssc = StreamingContext(conf.seconds, batch_size=conf.batchSize, num_batches=conf.numBatches,
+                           app_name=conf.appName(),
+                           max_batch_rows=int(getattr(cap, "max_rows", 0) or 0),
+                           max_batch_units=int(getattr(cap, "max_units", 0) or 0),
+                           clock=streaming_clock())
+    stream = ssc.twitterStream(make_source(conf.source, rate=conf.sourceRate, seed=conf.seed,
+                                           shard=rank, num_shards=world, start=0, batch_size=conf.batchSize)).cache()
+    job = ScoreJob(engine, conf.predictOut, rank, world)
+    stream.foreachRDD(job.on_batch)
+    ssc.start()
+    try:
+        ssc.awaitTermination()
+    except KeyboardInterrupt:
+        pass
+    finally:
+        ssc.stop()
+        job.close()
+    log.info("scored %d tweets in %d batches", job.scored, job.batches)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

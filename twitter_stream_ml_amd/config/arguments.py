@@ -137,6 +137,9 @@ _EXT_FLAGS = {
     "--seed": ("seed", int),
     "--batchTimeout": ("batchTimeout", float),
     "--checkReplicas": ("checkReplicas", int),
+    # apps/score.py (the training drivers ignore them)
+    "--model": ("model", str),
+    "--predictOut": ("predictOut", str),
 }
 
 _FLAG_LOOKUP = {}
@@ -194,6 +197,8 @@ class ConfArguments:
         self.seed = 42
         self.batchTimeout = 0.0
         self.checkReplicas = 0
+        self.model = ""        # apps/score.py: MLlib model directory to score with
+        self.predictOut = ""   # apps/score.py: directory of the per-batch prediction files
 
         self.usage = f"""
 Usage: python -m twitter_stream_ml_amd.apps.linear_regression
@@ -232,6 +237,8 @@ Usage: twtml-spark [options]
   --checkReplicas <n>                             verify DP replicas agree every n batches
   --plotPoints <n>                                points per Lightning append (default 10000; 0 = all)
   --legacyNumTextFeatures                         reproduce the reference bug: ignore -f
+  --model <dir>  --predictOut <dir>               scoring driver (apps.score / twtml-score): the MLlib
+                                                  model directory to load, where predictions go
   """
 
         if get_property("SPARK_SUBMIT") != "true":

@@ -180,6 +180,20 @@ class CpuLinearRegression:
         res.update(iterations=r.iterations, converged=r.converged, loss_history=r.loss_history)
         return res
 
+    def predict_batch(self, raw: RawBatch, apply_filter: bool = False,
+                      now_ms: Optional[int] = None) -> Dict[str, object]:
+        """Score a raw batch with the current weights without training on it
+        (the contract of ``DeviceLinearRegression.predict_batch``): fp64
+        ``x . w`` of every row, or of the rows the filter keeps."""
+        import time
+        t0 = time.perf_counter()
+        c = self.cfg
+        X, _, rows = featurize_columnar(raw, c.num_text_features, c.begin, c.end, now_ms=now_ms, hash=c.hash,
+                                        apply_filter=apply_filter)
+        pred = np.asarray(X @ self.w, dtype=np.float64).reshape(-1) if rows.shape[0] else np.zeros(0)
+        return {"n_raw": raw.n, "n_scored": int(rows.shape[0]), "rows": rows.astype(np.int64),
+                "pred": pred, "score_ms": (time.perf_counter() - t0) * 1e3}
+
     def synchronize(self) -> None:
         pass
 
@@ -276,7 +290,24 @@ class StreamingLinearRegressionWithSGD:
         stream.foreachRDD(op)
 
     def predictOn(self, stream):
-        return stream.map(lambda lp: self.latestModel().predict(lp.features if isinstance(lp, LabeledPoint) else lp))
+        """Predictions of every record of the stream.  With an engine attached
+        and a raw tweet stream (the RDD carries its ``RawBatch``) a batch is
+        one engine call -- ``predict_batch(raw)``: unfiltered fp64
+        predictions in record order, under the weights current when the RDD
+        is evaluated (lazily, like any RDD).  Otherwise ``model.predict`` is
+        mapped over the records (LabeledPoints or feature vectors)."""
+        from ..runtime.rdd import RDD
+
+        def per_record(lp):
+            return self.latestModel().predict(lp.features if isinstance(lp, LabeledPoint) else lp)
+
+        def op(rdd):
+            raw = getattr(rdd, "raw", None)
+            eng = self.engine
+            if eng is not None and isinstance(raw, RawBatch) and hasattr(eng, "predict_batch"):
+                return RDD(lambda: eng.predict_batch(raw, apply_filter=False)["pred"].tolist(), raw, rdd.num_slices)
+            return rdd.map(per_record)
+        return stream.transform(op)
 
     def predictOnValues(self, stream):
         return stream.map(lambda kv: (kv[0], self.latestModel().predict(kv[1])))

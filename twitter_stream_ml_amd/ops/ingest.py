@@ -61,15 +61,27 @@ class SlotPipeline:
         self.prefetched = 0        # batches whose H2D was issued ahead of time
         self.hits = 0              # ... and later consumed by take()
         self.orphaned = 0          # ... and skipped by the trained sequence (discarded)
+        self._scoring: set = set()  # slots lent to score-only batches (free_slot .. score_done)
 
     def _free_slot(self) -> int:
-        busy = {s for _, s in self._inflight.values()}
+        busy = {s for _, s in self._inflight.values()} | self._scoring
         for k in range(self.n_slots):
             s = (self._rr + k) % self.n_slots
             if s not in busy:
                 self._rr = (s + 1) % self.n_slots
                 return s
         raise RuntimeError("no free raw slot")
+
+    def free_slot(self) -> int:
+        """A slot no prefetched batch holds, for a batch outside the trained
+        sequence (score-only): the prefetched batches keep their slots and
+        their order.  Busy until ``score_done(slot)``."""
+        slot = self._free_slot()
+        self._scoring.add(slot)
+        return slot
+
+    def score_done(self, slot: int) -> None:
+        self._scoring.discard(slot)
 
     def _release(self, key: Hashable) -> None:
         _, slot = self._inflight.pop(key)

@@ -389,6 +389,32 @@ class DeviceLinearRegression:
         """Train on one micro-batch: uses its prefetched slot, else stages + H2D now."""
         return self.process(self._pipe.take(raw), raw.batch_time_ms, want_pred, plot_points)
 
+    # ---- inference (csrc/hip/score.hip) -----------------------------------
+    def predict_batch(self, raw: RawBatch, apply_filter: bool = False,
+                      now_ms: Optional[int] = None) -> Dict[str, object]:
+        """Score one raw micro-batch with the current weights, without
+        training on it: ``rows`` (int64 raw row ids, ascending) and ``pred``
+        (their fp64 predictions ``x . w``, nothing rounded; arrays owned by the
+        caller), ``n_raw``, ``n_scored``, ``score_ms`` (device time of the
+        scoring kernels).  ``apply_filter``: only the rows the training filter
+        keeps.  The batch is staged into a raw slot the training pipeline
+        holds no batch in and never enters the engine's prepare-ahead queue;
+        the model, the prefetched batches and a pending snapshot are left as
+        they are.  Call it from the thread that calls ``train_batch``."""
+        self.staging(0)._check(raw)   # the ValueError of training, before a slot is touched
+        if raw.n == 0:                # nothing is staged or launched
+            return {"n_raw": 0, "n_scored": 0, "rows": np.zeros(0, np.int64), "pred": np.zeros(0, np.float64),
+                    "score_ms": 0.0, "wall_ms": 0.0}
+        slot = self._pipe.free_slot()
+        try:
+            hb = self.staging(slot).load(raw, self.cfg.ingest)
+            self._eng.submit(hb._hb, int(hb.n), int(hb.bytes), int(slot), int(hb.ext_text),
+                             int(hb.batch_time_ms), False)
+            return self._eng.score(int(slot), int(raw.batch_time_ms if now_ms is None else now_ms),
+                                   bool(apply_filter))
+        finally:
+            self._pipe.score_done(slot)
+
     @property
     def h2d_bytes(self) -> int:
         """Host-to-device bytes submitted so far (every copy of every batch)."""
