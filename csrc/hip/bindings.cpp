@@ -37,6 +37,7 @@ static LRConfig lr_config(const py::dict& d) {
   GET(max_rows, int64_t) GET(max_units, int64_t) GET(sgd_grid, int32_t)
   GET(early_exit_depth, int32_t) GET(ablate, int32_t) GET(dedup, int32_t) GET(hybrid, int32_t) GET(lazy_idx, int32_t)
   GET(overlap, int32_t) GET(force_dp, int32_t) GET(comm_timing, int32_t) GET(raw_slots, int32_t)
+  GET(loss, int32_t) GET(label_threshold, int64_t) GET(threshold, double)
 #undef GET
   return c;
 }
@@ -344,11 +345,11 @@ PYBIND11_MODULE(_twtml_hip, m) {
            py::arg("host_batch"), py::arg("n"), py::arg("bytes"), py::arg("slot"), py::arg("ext_text") = 0,
            py::arg("now_ms") = 0, py::arg("train") = true)
       .def("score",
-           [](LREngine& e, int slot, int64_t now_ms, bool apply_filter) {
+           [](LREngine& e, int slot, int64_t now_ms, bool apply_filter, int link) {
              ScoreResult r;
              {
                py::gil_scoped_release nogil;
-               r = e.score(slot, now_ms, apply_filter);
+               r = e.score(slot, now_ms, apply_filter, link);
              }
              // copies owned by the caller (the engine's pinned buffer is reused)
              py::array_t<double> pred(r.n_scored);
@@ -368,9 +369,10 @@ PYBIND11_MODULE(_twtml_hip, m) {
              d["wall_ms"] = r.wall_ms;
              return d;
            },
-           py::arg("slot"), py::arg("now_ms"), py::arg("apply_filter") = false,
+           py::arg("slot"), py::arg("now_ms"), py::arg("apply_filter") = false, py::arg("link") = 0,
            "inference only: fp64 predictions of the batch in `slot` (submitted with train=False) under the "
-           "current weights; rows = raw row ids (ascending), pred in that order")
+           "current weights; rows = raw row ids (ascending), pred in that order; link 0 margin, "
+           "1 probability, 2 class (margin > logit(threshold))")
       .def("process",
            [](LREngine& e, int slot, int64_t now_ms, bool want_pred, int64_t plot_points) {
              BatchResult r;

@@ -246,6 +246,11 @@ LREngine::LREngine(int device, const LRConfig& cfg, std::shared_ptr<Comm> comm)
   if (cfg_.num_text_features <= 0) throw std::invalid_argument("numTextFeatures must be > 0");
   if (cfg_.max_rows <= 0 || cfg_.max_units < 0) throw std::invalid_argument("bad capacity");
   if (cfg_.max_rows >= (int64_t(1) << 31)) throw std::invalid_argument("max_rows must be < 2^31");
+  if (cfg_.loss != kLossSquared && cfg_.loss != kLossLogistic) throw std::invalid_argument("unknown loss");
+  // the logistic scales rest on |r| <= 1, i.e. on 0/1 labels
+  if (cfg_.loss == kLossLogistic && cfg_.label_threshold < 0)
+    throw std::invalid_argument("the logistic loss needs label_threshold >= 0 (0/1 labels)");
+  if (!(cfg_.threshold > 0.0 && cfg_.threshold < 1.0)) throw std::invalid_argument("threshold must be in (0, 1)");
   if (cfg_.fraction <= 0.0 || cfg_.fraction > 1.0 + 1e-12)
     throw std::invalid_argument("miniBatchFraction must be in (0, 1]");
   if (const char* v = std::getenv("TWTML_FORCE_TIERED")) force_tiered_ = v[0] == '1';   // tests
@@ -548,7 +553,8 @@ void LREngine::ensure_score() {
   p.counters = score_out_;
 }
 
-ScoreResult LREngine::score(int slot, int64_t now_ms, bool apply_filter) {
+ScoreResult LREngine::score(int slot, int64_t now_ms, bool apply_filter, int link) {
+  if (link < kLinkMargin || link > kLinkClass) throw std::invalid_argument("score(): unknown link");
   TraceRange tr("twtml.lr.score");
   TWTML_HIP_CHECK(hipSetDevice(device_));
   const auto t_in = std::chrono::steady_clock::now();
@@ -572,7 +578,7 @@ ScoreResult LREngine::score(int slot, int64_t now_ms, bool apply_filter) {
   launch_score_init(score_dp_, s);
   launch_filter_sort(b, score_dp_, fp, s);
   launch_chunk_layout(b, score_dp_, s);
-  launch_score(b, score_dp_, fp, lower_page_, lower_blocks_, sgd_.w64, pred, rows, s);
+  launch_score(b, score_dp_, fp, lower_page_, lower_blocks_, sgd_.w64, pred, rows, s, link, logit_threshold());
   TWTML_HIP_CHECK(hipEventRecord(score_ev_[1], s));
   raw_.release_slot(slot, s);   // the raw slot may be overwritten now
   const size_t words = 8 + size_t(apply_filter ? 2 * n : n);
@@ -620,6 +626,7 @@ void LREngine::prepare_local(PrepBuf& pb, int slot, int64_t now_ms, hipStream_t 
 
   FeaturizeParams fp{cfg_.num_text_features, cfg_.hash_kind, cfg_.require_retweet,
                      cfg_.range_filter, cfg_.begin, cfg_.end, now_ms};
+  fp.label_threshold = cfg_.label_threshold;
   launch_prep_init(prep, pb.n_global, 2 * world + 2, s, pb.bounds, kBoundsLen);
   launch_filter_sort(b, prep, fp, s);
   launch_chunk_layout(b, prep, s);
@@ -890,7 +897,7 @@ BatchResult LREngine::train(PrepBuf& pb, bool want_pred, int64_t plot_points) {
   TraceRange tr_train("twtml.lr.train");   // GD iterations (host enqueue + early-stop polling)
 
   const int64_t nl = sgd_.nl;
-  int grid = cfg_.sgd_grid > 0 ? cfg_.sgd_grid : sgd_iter_grid(nl, res.n_kept, num_cu_, prep.hybrid != 0);
+  int grid = cfg_.sgd_grid > 0 ? cfg_.sgd_grid : sgd_iter_grid(nl, res.n_kept, num_cu_, prep.hybrid != 0, cfg_.loss);
   sgd_.pstride = sgd_part_stride(nl);
   sgd_.nparts = sgd_partials(nl, u16, grid);
   ensure_part(int64_t(sgd_.nparts) * sgd_.pstride);
@@ -905,6 +912,8 @@ BatchResult LREngine::train(PrepBuf& pb, bool want_pred, int64_t plot_points) {
   sp.ablate = cfg_.ablate;
   sp.dp = dp_ ? 1 : 0;
   sp.rank0 = (comm_ ? comm_->rank() : 0) == 0 ? 1 : 0;
+  sp.loss = cfg_.loss;
+  sp.logit_thr = float(logit_threshold());
   const int64_t n_far = kNumNumeric + nU - sgd_.far_base;
   res.diverged = diverged_;
   int comm_iters = 0;   // DP: gradient all-reduces issued for this batch

@@ -16,6 +16,7 @@
 // is fused into iteration 1, so it sees the weights before training on the
 // batch (LinearRegression.scala:53-86 ordering).
 #pragma once
+#include <cmath>
 #include <hip/hip_runtime.h>
 
 #include <condition_variable>
@@ -58,6 +59,9 @@ struct LRConfig {
                                  // all-reduce) even with a world-1 communicator (also TWTML_FORCE_DP=1)
   int32_t comm_timing = 0;       // DP: time the per-iteration gradient all-reduce (events)
   int32_t raw_slots = kDefaultRawSlots;   // device raw-batch slots (H2D run-ahead depth + 1)
+  int32_t loss = 0;              // kLossSquared (linear regression) / kLossLogistic (binary classifier)
+  int64_t label_threshold = -1;  // < 0: y = retweetCount; else y = retweetCount >= label_threshold
+  double threshold = 0.5;        // logistic: class 1 when the probability exceeds it (0 < threshold < 1)
 };
 
 // Pinned staging buffer of one raw batch in the wire format
@@ -248,7 +252,8 @@ class LREngine {
   // no collective is issued (a DP rank may score between any two process()
   // calls, on its own).  Scratch is allocated by the first call.
   // score() and process() must be called from the same thread.
-  ScoreResult score(int slot, int64_t now_ms, bool apply_filter);
+  // link: kLinkMargin / kLinkProbability / kLinkClass (kernels.h), applied on the device
+  ScoreResult score(int slot, int64_t now_ms, bool apply_filter, int link = 0);
   // Forget a submitted batch that will not be processed (one GPU only): the
   // slot may be submitted again afterwards (ops/ingest.py SlotPipeline).
   void discard(int slot);
@@ -256,6 +261,8 @@ class LREngine {
   void set_weights(const double* w, int64_t n);
   void get_weights(double* w, int64_t n) const;
   int64_t num_weights() const { return cfg_.num_text_features + kNumNumeric; }
+  // logit(threshold): the margin above which a row is class 1 (exactly 0 at 0.5)
+  double logit_threshold() const { return std::log(cfg_.threshold / (1.0 - cfg_.threshold)); }
   // Device bytes allocated on demand: by the first tiered batch (per prepared
   // buffer: the entry-sized far lists and CSC, the slot-sized tier arrays; the trainer's residual row
   // buffer) and by the first checkpoint snapshot ((index, value) pairs for

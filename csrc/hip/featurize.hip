@@ -894,7 +894,8 @@ __device__ __forceinline__ void row_scalars(const DevRawBatch& b, const DevPrepa
                                             int64_t row, int32_t kidx) {
   const int64_t cap = p.cap_rows16;
   if (valid) {
-    p.y[pos] = float(raw_scalar(b, 0, row));
+    const int64_t rt = raw_scalar(b, 0, row);
+    p.y[pos] = fp.label_threshold < 0 ? float(rt) : (rt >= fp.label_threshold ? 1.f : 0.f);
     const double fol = double(raw_scalar(b, 1, row)), fav = double(raw_scalar(b, 2, row));
     const double fri = double(raw_scalar(b, 3, row));
     const double age = double(fp.now_ms - raw_scalar(b, 4, row));

@@ -200,6 +200,8 @@ struct FeaturizeParams {
   // chunk slice [c_lo, c_hi) of one launch (prep kernels split into slices,
   // see prep_slices())
   int64_t c_lo = 0, c_hi = INT64_MAX;
+  // label: < 0 float(retweetCount) (regression); else retweetCount >= label_threshold ? 1 : 0
+  int64_t label_threshold = -1;
 };
 
 // lower-casing tables, allocated from the caller's arena
@@ -246,9 +248,13 @@ void launch_remap_hybrid(const DevPrepared& p, int64_t entries, int64_t ns, int6
 // launch_filter_sort, launch_chunk_layout, launch_score.
 void launch_score_init(const DevPrepared& p, hipStream_t s);
 // pred[k] (and rows[k] = raw row id, if rows) of kept row k, in kept (=
-// ascending raw row) order
+// ascending raw row) order.  link (applied per row to the margin m, in fp64):
+// kLinkMargin m itself, kLinkProbability 1 / (1 + exp(-m)), kLinkClass
+// m > logit_thr ? 1 : 0.
+constexpr int kLinkMargin = 0, kLinkProbability = 1, kLinkClass = 2;
 void launch_score(const DevRawBatch& b, const DevPrepared& p, const FeaturizeParams& fp, const uint8_t* lower_page,
-                  const uint16_t* lower_blocks, const double* w64, double* pred, int64_t* rows, hipStream_t s);
+                  const uint16_t* lower_blocks, const double* w64, double* pred, int64_t* rows, hipStream_t s,
+                  int link = kLinkMargin, double logit_thr = 0.0);
 
 // Exclusive int64 scan (in place safe); tsum: ceil(n / 2048) + 2 scratch.
 void launch_scan_excl(const int64_t* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum, hipStream_t s,
@@ -370,6 +376,10 @@ constexpr int kStateLen = 12;
 // bounds: [0] max bigram count of a row, [1] max |y|, [2..5] max |n_k|
 constexpr int kBoundsLen = 8;
 
+// Loss of the GD iteration: LeastSquaresGradient (r = x.w - y, loss r^2 / 2)
+// or the binary LogisticGradient (r = sigma(x.w) - y, loss log1pExp).
+constexpr int kLossSquared = 0, kLossLogistic = 1;
+
 struct SgdParams {
   double step_size;
   double fraction;
@@ -382,6 +392,8 @@ struct SgdParams {
   int32_t ablate;       // perf diagnostics (hybrid): 7 = no chunks (fixed cost), 8 = no far forward
   int32_t dp;           // world > 1: convergence verdicts travel in the gradient all-reduce
   int32_t rank0;        // this rank's verdict is the one that counts (DP)
+  int32_t loss;         // kLossSquared / kLossLogistic (the iteration kernels' template parameter)
+  float logit_thr;      // logistic: the class prediction of iteration 1 is dot > logit(threshold)
 };
 
 void launch_gather_w(const DevSgd& d, const DevPrepared& p, hipStream_t s);
@@ -416,7 +428,7 @@ void launch_batch_bounds(const DevPrepared& p, double* out, hipStream_t s, bool 
 int sgd_lds_rep(int64_t ns);
 // the hybrid iteration kernel's LDS (gradient replicas + hot partials) fits
 bool sgd_hybrid_fits(int64_t ns);
-int sgd_iter_grid(int64_t ns, int64_t n_kept, int num_cu, bool hybrid);
+int sgd_iter_grid(int64_t ns, int64_t n_kept, int num_cu, bool hybrid, int loss = kLossSquared);
 
 // ---------------------------------------------------------------------------
 // DP batch preparation (dp_prep.hip): one packet per rank, all-gathered once.

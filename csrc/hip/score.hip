@@ -54,17 +54,25 @@ __device__ __forceinline__ double quad_sum_f64(double v) {
   return v;
 }
 
-// Lane t == 0 of a row: numeric part (fp64, MllibHelper.scala:58-71) and the
-// store at the row's kept index.
+// What a score is of the margin (launch_score's link).
+struct ScoreLink {
+  int32_t link;
+  double logit_thr;
+};
+
+// Lane t == 0 of a row: numeric part (fp64, MllibHelper.scala:58-71), the
+// link, and the store at the row's kept index.
 __device__ __forceinline__ void score_store(const DevRawBatch& b, const FeaturizeParams& fp, const double* w64,
                                             double text, int64_t row, int32_t kidx, double* pred,
-                                            int64_t* rows) {
+                                            int64_t* rows, const ScoreLink& lk) {
   const double* wn = w64 + fp.num_text_features;
   double p = text;
   p += (double(raw_scalar(b, 1, row)) * 1e-12) * wn[0];
   p += (double(raw_scalar(b, 2, row)) * 1e-12) * wn[1];
   p += (double(raw_scalar(b, 3, row)) * 1e-12) * wn[2];
   p += (double(fp.now_ms - raw_scalar(b, 4, row)) * 1e-14) * wn[3];
+  if (lk.link == kLinkProbability) p = 1.0 / (1.0 + exp(-p));   // exp overflows to +inf: exactly 0
+  else if (lk.link == kLinkClass) p = p > lk.logit_thr ? 1.0 : 0.0;
   pred[kidx] = p;
   if (rows) rows[kidx] = row;
 }
@@ -76,7 +84,7 @@ __device__ __forceinline__ void score_store(const DevRawBatch& b, const Featuriz
 // profiles/README.md "Scoring".)
 __global__ __launch_bounds__(kBlock) void k_score_narrow(DevRawBatch b, DevPrepared p, FeaturizeParams fp,
                                                          const double* w64, double* pred, int64_t* rows,
-                                                         int64_t cmax) {
+                                                         int64_t cmax, ScoreLink lk) {
   const int64_t n_kept = p.counters[0];
   const int t = lane_id() % kLanesPerRow;
   const int64_t wave = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / kWave;
@@ -105,13 +113,14 @@ __global__ __launch_bounds__(kBlock) void k_score_narrow(DevRawBatch b, DevPrepa
         if (g * kGroup + k < L.my) acc += wv[k];
     }
     acc = quad_sum_f64(acc);
-    if (t == 0 && L.valid) score_store(b, fp, w64, acc, L.row, L.kidx, pred, rows);
+    if (t == 0 && L.valid) score_store(b, fp, w64, acc, L.row, L.kidx, pred, rows, lk);
   }
 }
 
 __global__ __launch_bounds__(kBlock) void k_score(DevRawBatch b, DevPrepared p, FeaturizeParams fp,
                                                   const uint8_t* lpage, const uint16_t* lblocks,
-                                                  const double* w64, double* pred, int64_t* rows, int64_t cmax) {
+                                                  const double* w64, double* pred, int64_t* rows, int64_t cmax,
+                                                  ScoreLink lk) {
   __shared__ uint32_t stage[kBlock / kWave][kRowsPerChunk * kStageStride];
   __shared__ __attribute__((aligned(16))) uint8_t lpage_s[256];
   __shared__ __attribute__((aligned(16))) uint16_t lblk_s[kLowerLdsBlocks * 256];
@@ -178,7 +187,7 @@ __global__ __launch_bounds__(kBlock) void k_score(DevRawBatch b, DevPrepared p, 
     }
     __builtin_amdgcn_wave_barrier();   // LDS reads of this chunk precede the next staging
     acc = quad_sum_f64(acc);
-    if (t == 0 && valid) score_store(b, fp, w64, acc, row, kidx, pred, rows);
+    if (t == 0 && valid) score_store(b, fp, w64, acc, row, kidx, pred, rows, lk);
   }
 }
 
@@ -197,13 +206,15 @@ void launch_score_init(const DevPrepared& p, hipStream_t s) {
 }
 
 void launch_score(const DevRawBatch& b, const DevPrepared& p, const FeaturizeParams& fp, const uint8_t* lpage,
-                  const uint16_t* lblocks, const double* w64, double* pred, int64_t* rows, hipStream_t s) {
+                  const uint16_t* lblocks, const double* w64, double* pred, int64_t* rows, hipStream_t s,
+                  int link, double logit_thr) {
   const int64_t cmax = (b.n + kRowsPerChunk - 1) / kRowsPerChunk;
   if (cmax == 0) return;
   int grid = ceil_div(cmax, kBlock / kWave);
   if (grid > 2048) grid = 2048;
-  TWTML_LAUNCH(k_score_narrow, dim3(grid), dim3(kBlock), 0, s, b, p, fp, w64, pred, rows, cmax);
-  TWTML_LAUNCH(k_score, dim3(grid), dim3(kBlock), 0, s, b, p, fp, lpage, lblocks, w64, pred, rows, cmax);
+  const ScoreLink lk{link, logit_thr};
+  TWTML_LAUNCH(k_score_narrow, dim3(grid), dim3(kBlock), 0, s, b, p, fp, w64, pred, rows, cmax, lk);
+  TWTML_LAUNCH(k_score, dim3(grid), dim3(kBlock), 0, s, b, p, fp, lpage, lblocks, w64, pred, rows, cmax, lk);
 }
 
 }  // namespace twtml

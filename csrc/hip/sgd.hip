@@ -5,6 +5,10 @@
 //   g   = sum_i r_i x_i          (treeAggregate -> here LDS-privatised scatter)
 //   w  -= (step / sqrt(i)) g / m (SimpleUpdater, U7)
 //   stop when ||dw|| < tol * max(||w||, 1) once two updates exist.
+// With LOSS = kLossLogistic (StreamingLogisticRegressionWithSGD, binary
+// LogisticGradient, regParam 0) only the row epilogue differs:
+//   r_i = 1 / (1 + exp(-x_i . w)) - y_i, y_i in {0, 1}   (row_residual)
+// and everything downstream of q = rint(r 2^S) is the same code.
 //
 // The model works in the batch's *compact active space*: slots 0..3 are the
 // numeric features (F..F+3), slots 4.. the text features touched by the
@@ -129,7 +133,7 @@ __device__ __forceinline__ int ceil_log2(double x) {    // x >= 1
 struct IterScale {
   float wscale, wunscale;   // 2^K, 2^-K
   float qscale;             // 2^S
-  float lhalf;              // 2^(L/2)
+  float lhalf;              // squared loss: 2^(L/2) (applied to r before squaring); logistic: 2^L
   float nscale[kNumNumeric];    // 2^N_k
   int K, S, L, N[kNumNumeric];
   double B;
@@ -138,13 +142,27 @@ struct IterScale {
 
 // Deterministic in (max |w_text|, numeric weights, batch bounds, m): every
 // workgroup, every iteration kernel and every DP rank derives the same.
+//
+// LOSS == kLossLogistic: the residual sigma(x.w) - y has |r| <= 1 whatever the
+// weights are, so S and N_k come from B_r = 1 (+ the rounding allowance) and
+// do not coarsen as |w| grows; the row loss log(1 + exp(-+x.w)) is bounded by
+// the |dot| bound + ln 2 and gets its own scale 2^L (not a square: lhalf
+// holds 2^L).  K and the diverged rule are those of the squared loss.
+template <int LOSS>
 __device__ IterScale sgd_scales(const double* bd, double maxw, const float* wn) {
   IterScale s{};
   double B = bd[0] * maxw + bd[1];
 #pragma unroll
   for (int k = 0; k < kNumNumeric; ++k) B += bd[2 + k] * fabs(double(wn[k]));
   B = B * (1.0 + 1.0 / 1024.0) + 1.0;   // fp32 rounding of the dot, rint of the weights
-  s.B = B;
+  double Bl = 0.0;                      // logistic: bound of a row's loss
+  if (LOSS == kLossLogistic) {
+    double D = bd[0] * maxw;
+#pragma unroll
+    for (int k = 0; k < kNumNumeric; ++k) D += bd[2 + k] * fabs(double(wn[k]));
+    Bl = D * (1.0 + 1.0 / 1024.0) + 1.0 + 0.6931471805599453;
+  }
+  s.B = LOSS == kLossLogistic ? 1.0 + 1.0 / 1024.0 : B;
   // diverged: the residual bound (or the weights) left any usable range
   s.bad = !(B < 1e30) || !(maxw < 1e30) || !(B == B);
   if (s.bad) {
@@ -161,7 +179,7 @@ __device__ IterScale sgd_scales(const double* bd, double maxw, const float* wn) 
     if (T > 0.0) K = min(K, 29 - floor_log2(T));
   }
   K = K < -120 ? -120 : (K > 120 ? 120 : K);
-  const int eb = floor_log2(B) + 1;                     // B < 2^eb
+  const int eb = floor_log2(s.B) + 1;                   // B < 2^eb
   // Per row |q|, |r n_k| 2^N_k and r^2 2^L stay <= 2^22: kHotFlush rows of
   // them (x count 15 for q) fit the kernels' int32 accumulators, and m rows
   // (m < 2^31) the int64 sums.
@@ -172,6 +190,10 @@ __device__ IterScale sgd_scales(const double* bd, double maxw, const float* wn) 
   s.wunscale = ldexpf(1.f, -K);
   s.qscale = ldexpf(1.f, s.S);
   s.lhalf = ldexpf(1.f, 11 - eb);
+  if (LOSS == kLossLogistic) {
+    s.L = 22 - (floor_log2(Bl) + 1);                    // loss 2^L <= Bl 2^L < 2^22
+    s.lhalf = ldexpf(1.f, s.L);
+  }
 #pragma unroll
   for (int k = 0; k < kNumNumeric; ++k) {
     const double nm = bd[2 + k];
@@ -300,6 +322,7 @@ __device__ bool sgd_converged_wave(const DevSgd& d, int it, double tol, double* 
 // state[7] set instead of state[1].  DP ranks only skip the pass on their
 // own verdict (state[8] = iteration): k_sgd_reduce puts rank 0's into the
 // gradient all-reduce and k_sgd_update acts on the agreed value.
+template <int LOSS>
 __device__ bool sgd_prologue(const DevSgd& d, const SgdParams& sp, int* flag, IterScale* sc) {
   if (threadIdx.x < kWave) {
     const int it = sp.iteration;
@@ -316,7 +339,7 @@ __device__ bool sgd_prologue(const DevSgd& d, const SgdParams& sp, int* flag, It
     const bool done = st0 != 0.0;
     bool stop = done;
     if (!done) {
-      const IterScale s = sgd_scales(bd, maxw, wn);
+      const IterScale s = sgd_scales<LOSS>(bd, maxw, wn);
       stop = conv || s.bad;
       if (blockIdx.x == 0 && threadIdx.x == 0) {
         double* rec = sgd_rec(d, it);
@@ -380,7 +403,14 @@ __device__ __forceinline__ int32_t row_total(int32_t v) {
 // rounded prediction to pbuf (k_batch_stats sums the moments exactly) and
 // the plot's pred / real; accumulates numeric-feature gradients, loss and
 // the sampled count.  Returns r (0 for rows outside the batch / the sample).
-template <bool STATS, bool SAMPLE>
+//
+// LOSS == kLossLogistic (MLlib LogisticGradient, binary): margin = -dot,
+// r = 1 / (1 + exp(margin)) - y, row loss log1pExp(margin) for y > 0 and
+// log1pExp(margin) - margin otherwise; the STATS prediction is the class
+// dot > logit(threshold).  Everything goes through e = exp(-|dot|) in (0, 1]:
+// nothing overflows, and once e underflows (|dot| > ~104) the residual is
+// exactly -y or 1 - y and the loss exactly |dot| or 0.
+template <int LOSS, bool STATS, bool SAMPLE>
 __device__ __forceinline__ float row_residual(int32_t dot_fix, const RowIn& ri, int64_t pos, int t,
                                               const DevSgd& d, const DevPrepared& p, const SgdParams& sp,
                                               int64_t n_kept, const LaneScale& sc, RowAcc& acc) {
@@ -393,12 +423,26 @@ __device__ __forceinline__ float row_residual(int32_t dot_fix, const RowIn& ri, 
   bool in = valid;
   if (SAMPLE && valid)
     in = sample_uniform(uint64_t(42 + sp.iteration), uint64_t(sp.row_offset + p.perm[pos])) < sp.fraction;
-  const float r = in ? dot - ri.y : 0.f;
+  float r, lrow = 0.f;
+  if (LOSS == kLossLogistic) {
+    const float e = expf(-fabsf(dot));
+    const float inv = 1.f / (1.f + e);
+    const float sig = dot >= 0.f ? inv : e * inv;
+    r = in ? sig - ri.y : 0.f;
+    // log1pExp(margin) = max(margin, 0) + log1p(e); minus margin for y == 0
+    const float pos = ri.y > 0.f ? fmaxf(-dot, 0.f) : fmaxf(dot, 0.f);
+    // 1 + e in [1, 2]: the hardware log's error and the rounding of 1 + e are
+    // absolute errors < 2^-23, below the loss quantum 2^-L (L <= 21)
+    lrow = in ? pos + __logf(1.f + e) : 0.f;
+  } else {
+    r = in ? dot - ri.y : 0.f;
+  }
   if (t == 0) {
     if (STATS && valid) {
       // round half away of an fp32 value is an fp32 value (|dot| >= 2^23 is
       // already an integer), so the float holds the prediction exactly
-      const float pr = float(round_half_away(double(dot)));
+      const float pr = LOSS == kLossLogistic ? (dot > sp.logit_thr ? 1.f : 0.f)
+                                             : float(round_half_away(double(dot)));
       d.pbuf[pos] = pr;
       if (sp.want_pred) {
         d.pred_out[p.perm[pos]] = pr;
@@ -406,8 +450,12 @@ __device__ __forceinline__ float row_residual(int32_t dot_fix, const RowIn& ri, 
       }
     }
     if (SAMPLE && in) ++acc.msum;
-    const float u = r * sc.lhalf;
-    acc.ql += __float2int_rn(u * u);
+    if (LOSS == kLossLogistic) {
+      acc.ql += __float2int_rn(lrow * sc.lhalf);
+    } else {
+      const float u = r * sc.lhalf;
+      acc.ql += __float2int_rn(u * u);
+    }
   }
   acc.qn += __float2int_rn((r * ri.nt) * sc.nsc_t);
   return r;
@@ -460,13 +508,13 @@ __device__ __forceinline__ int32_t w_to_fix(float w, float wscale) {
 // ---------------------------------------------------------------------------
 constexpr int kIterBlock = 1024;
 
-template <bool STATS, bool SAMPLE, int REP, bool CNT>
+template <int LOSS, bool STATS, bool SAMPLE, int REP, bool CNT>
 __global__ __launch_bounds__(kIterBlock) void k_sgd_iter_lds(DevSgd d, DevPrepared p, SgdParams sp) {
   extern __shared__ __attribute__((aligned(16))) int32_t lds[];
   __shared__ int64_t wsc[kIterBlock / kWave][kPartVals];
   __shared__ int stop_flag;
   __shared__ IterScale scs;
-  if (sgd_prologue(d, sp, &stop_flag, &scs)) return;   // converged / finished: the rest of the batch is a no-op
+  if (sgd_prologue<LOSS>(d, sp, &stop_flag, &scs)) return;   // converged / finished: the rest of the batch is a no-op
   const int lane = lane_id();
   const int r = lane / kLanesPerRow, t = lane % kLanesPerRow;
   const LaneScale sc = lane_scale(scs, d, t);
@@ -539,7 +587,7 @@ __global__ __launch_bounds__(kIterBlock) void k_sgd_iter_lds(DevSgd d, DevPrepar
         }
       }
       const int32_t dot = row_total(d0 + d1);
-      const float res = row_residual<STATS, SAMPLE>(dot, ri, pos, t, d, p, sp, n_kept, sc, acc);
+      const float res = row_residual<LOSS, STATS, SAMPLE>(dot, ri, pos, t, d, p, sp, n_kept, sc, acc);
       if (res != 0.f && sp.ablate == 0) {
         const unsigned long long q = (unsigned long long)(long long)__float2int_rn(res * sc.qscale);
 #pragma unroll
@@ -568,7 +616,7 @@ __global__ __launch_bounds__(kIterBlock) void k_sgd_iter_lds(DevSgd d, DevPrepar
         for (int e = 0; e < 8; ++e) dot += wl[s[e]];
       }
       dot = row_total(dot);
-      const float res = row_residual<STATS, SAMPLE>(dot, ri, pos, t, d, p, sp, n_kept, sc, acc);
+      const float res = row_residual<LOSS, STATS, SAMPLE>(dot, ri, pos, t, d, p, sp, n_kept, sc, acc);
       if (res != 0.f) {
         const unsigned long long q = (unsigned long long)(long long)__float2int_rn(res * sc.qscale);
         for (int32_t g = 0; g < L8; ++g) {
@@ -701,7 +749,7 @@ __device__ __forceinline__ void hot_digits(const DevPrepared& p, const int32_t* 
 // TIERED: the chunk's far entries (p.fslot list, weights from global memory)
 // join the row dots through the per-wave LDS row sums fdot (int32), and every
 // row's residual goes to d.rbuf for the far backward (k_far_grad).
-template <bool STATS, bool SAMPLE, int REP, bool TIERED>
+template <int LOSS, bool STATS, bool SAMPLE, int REP, bool TIERED>
 __device__ __forceinline__ void hyb_pass(const DevSgd& d, const DevPrepared& p, const SgdParams& sp,
                                          const LaneScale& sc, const int32_t* wl, unsigned long long* gl,
                                          const uint32_t* whl, unsigned long long* hsum,
@@ -829,7 +877,7 @@ __device__ __forceinline__ void hyb_pass(const DevSgd& d, const DevPrepared& p, 
         }
       }
       const int32_t dot = row_total(d0 + d1);
-      const float res = row_residual<STATS, SAMPLE>(dot, ri, pos, t, d, p, sp, n_kept, sc, acc);
+      const float res = row_residual<LOSS, STATS, SAMPLE>(dot, ri, pos, t, d, p, sp, n_kept, sc, acc);
       if (TIERED && t == 0) d.rbuf[pos] = res;
       const int32_t q = __float2int_rn(res * sc.qscale);
       // unconditional (q = 0 adds nothing): the accumulators then need no
@@ -866,7 +914,7 @@ __device__ __forceinline__ void hyb_pass(const DevSgd& d, const DevPrepared& p, 
         for (int e = 0; e < 8; ++e) dot += wl[s[e]];
       }
       dot = row_total(dot);
-      const float res = row_residual<STATS, SAMPLE>(dot, ri, pos, t, d, p, sp, n_kept, sc, acc);
+      const float res = row_residual<LOSS, STATS, SAMPLE>(dot, ri, pos, t, d, p, sp, n_kept, sc, acc);
       if (TIERED && t == 0) d.rbuf[pos] = res;
       if (res != 0.f) {
         const unsigned long long q = (unsigned long long)(long long)__float2int_rn(res * sc.qscale);
@@ -957,7 +1005,7 @@ __device__ __forceinline__ void hyb_lds_init(const DevPrepared& p, const float* 
   __syncthreads();
 }
 
-template <bool STATS, bool SAMPLE, int REP, bool TIERED>
+template <int LOSS, bool STATS, bool SAMPLE, int REP, bool TIERED>
 __global__ __launch_bounds__(kIterBlock) void k_sgd_iter_hyb(DevSgd d, DevPrepared p, SgdParams sp) {
   extern __shared__ __attribute__((aligned(16))) int32_t lds[];
   __shared__ int64_t wsc[kIterBlock / kWave][kPartVals];
@@ -972,15 +1020,15 @@ __global__ __launch_bounds__(kIterBlock) void k_sgd_iter_hyb(DevSgd d, DevPrepar
     tst = d.tdbg + (int64_t(sp.iteration) * 2 + (blockIdx.x == 0 ? 0 : 1)) * 8;
   if (tst) tst[0] = __builtin_amdgcn_s_memrealtime();
   kdbg_stamp(d.kdbg, sp.iteration, 0, 0);
-  if (sgd_prologue(d, sp, &stop_flag, &scs)) return;
+  if (sgd_prologue<LOSS>(d, sp, &stop_flag, &scs)) return;
   const LaneScale sc = lane_scale(scs, d, lane_id() % kLanesPerRow);
   if (tst) tst[1] = __builtin_amdgcn_s_memrealtime();
   int32_t* wl = lds;
   unsigned long long* gl = reinterpret_cast<unsigned long long*>(lds + d.nl);
   hyb_lds_init<REP>(p, d.wc32, d.nl, d.far_base, sc.wscale, wl, gl, whl, hsum, &wctr);
   if (tst) tst[2] = __builtin_amdgcn_s_memrealtime();
-  hyb_pass<STATS, SAMPLE, REP, TIERED>(d, p, sp, sc, wl, gl, whl, hsum, wsc,
-                                       d.part + int64_t(blockIdx.x) * d.pstride, &wctr, fdot, tst);
+  hyb_pass<LOSS, STATS, SAMPLE, REP, TIERED>(d, p, sp, sc, wl, gl, whl, hsum, wsc,
+                                             d.part + int64_t(blockIdx.x) * d.pstride, &wctr, fdot, tst);
   if (tst) tst[6] = __builtin_amdgcn_s_memrealtime();
   if (d.kdbg) {
     __syncthreads();
@@ -1027,13 +1075,13 @@ bool sgd_hybrid_fits(int64_t ns) {
   return ns <= kMaxHybridSlots && rep > 0 && lds_bytes(ns, rep) + statics <= 160 * 1024 - 1024;
 }
 
-template <bool STATS, bool SAMPLE>
+template <int LOSS, bool STATS, bool SAMPLE>
 static void launch_iter_t(const DevSgd& d, const DevPrepared& p, const SgdParams& sp, bool u16,
                           int rep, int grid, hipStream_t s) {
   if (u16 && rep > 0 && p.hybrid) {
     const size_t lds = size_t(lds_bytes(d.nl, rep));
 #define TWTML_HYB(R, T) \
-  TWTML_LAUNCH((k_sgd_iter_hyb<STATS, SAMPLE, R, T>), dim3(grid), dim3(kIterBlock), lds, s, d, p, sp)
+  TWTML_LAUNCH((k_sgd_iter_hyb<LOSS, STATS, SAMPLE, R, T>), dim3(grid), dim3(kIterBlock), lds, s, d, p, sp)
     const bool tiered = p.tiered != 0;
     switch (rep) {
       case 8: if (tiered) TWTML_HYB(8, true); else TWTML_HYB(8, false); break;
@@ -1045,7 +1093,7 @@ static void launch_iter_t(const DevSgd& d, const DevPrepared& p, const SgdParams
   } else if (u16 && rep > 0) {
     const size_t lds = size_t(lds_bytes(d.nl, rep));
 #define TWTML_ITER(R, C) \
-  TWTML_LAUNCH((k_sgd_iter_lds<STATS, SAMPLE, R, C>), dim3(grid), dim3(kIterBlock), lds, s, d, p, sp)
+  TWTML_LAUNCH((k_sgd_iter_lds<LOSS, STATS, SAMPLE, R, C>), dim3(grid), dim3(kIterBlock), lds, s, d, p, sp)
     const bool cnt = p.dedup != 0;
     switch (rep) {
       case 8: if (cnt) TWTML_ITER(8, true); else TWTML_ITER(8, false); break;
@@ -1064,16 +1112,17 @@ static void launch_iter_t(const DevSgd& d, const DevPrepared& p, const SgdParams
 // is one per CU -- an LDS-only estimate launched 2-3 rounds of workgroups
 // for mid-sized active sets, each round paying the full per-iteration
 // overhead and adding partial rows).
-static int iter_blocks_per_cu(int64_t ns, int rep, bool hybrid) {
+template <int LOSS>
+static int iter_blocks_per_cu_t(int64_t ns, int rep, bool hybrid) {
   const size_t lds = size_t(lds_bytes(ns, rep));
   int n = 0;
   hipError_t e = hipSuccess;
 #define TWTML_OCC(K) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K, kIterBlock, lds)
   switch (rep) {
-    case 8: if (hybrid) TWTML_OCC((k_sgd_iter_hyb<false, false, 8, true>)); else TWTML_OCC((k_sgd_iter_lds<false, false, 8, false>)); break;
-    case 4: if (hybrid) TWTML_OCC((k_sgd_iter_hyb<false, false, 4, true>)); else TWTML_OCC((k_sgd_iter_lds<false, false, 4, false>)); break;
-    case 2: if (hybrid) TWTML_OCC((k_sgd_iter_hyb<false, false, 2, true>)); else TWTML_OCC((k_sgd_iter_lds<false, false, 2, false>)); break;
-    default: if (hybrid) TWTML_OCC((k_sgd_iter_hyb<false, false, 1, true>)); else TWTML_OCC((k_sgd_iter_lds<false, false, 1, false>)); break;
+    case 8: if (hybrid) TWTML_OCC((k_sgd_iter_hyb<LOSS, false, false, 8, true>)); else TWTML_OCC((k_sgd_iter_lds<LOSS, false, false, 8, false>)); break;
+    case 4: if (hybrid) TWTML_OCC((k_sgd_iter_hyb<LOSS, false, false, 4, true>)); else TWTML_OCC((k_sgd_iter_lds<LOSS, false, false, 4, false>)); break;
+    case 2: if (hybrid) TWTML_OCC((k_sgd_iter_hyb<LOSS, false, false, 2, true>)); else TWTML_OCC((k_sgd_iter_lds<LOSS, false, false, 2, false>)); break;
+    default: if (hybrid) TWTML_OCC((k_sgd_iter_hyb<LOSS, false, false, 1, true>)); else TWTML_OCC((k_sgd_iter_lds<LOSS, false, false, 1, false>)); break;
   }
 #undef TWTML_OCC
   if (e != hipSuccess || n < 1) {
@@ -1083,10 +1132,16 @@ static int iter_blocks_per_cu(int64_t ns, int rep, bool hybrid) {
   return n;
 }
 
-int sgd_iter_grid(int64_t ns, int64_t n_kept, int num_cu, bool hybrid) {
+// the instantiation of the loss that is launched
+static int iter_blocks_per_cu(int64_t ns, int rep, bool hybrid, int loss) {
+  return loss == kLossLogistic ? iter_blocks_per_cu_t<kLossLogistic>(ns, rep, hybrid)
+                               : iter_blocks_per_cu_t<kLossSquared>(ns, rep, hybrid);
+}
+
+int sgd_iter_grid(int64_t ns, int64_t n_kept, int num_cu, bool hybrid, int loss) {
   const int rep = sgd_lds_rep(ns);
   int per_cu = 2;
-  if (rep > 0) per_cu = std::min(4, iter_blocks_per_cu(ns, rep, hybrid));
+  if (rep > 0) per_cu = std::min(4, iter_blocks_per_cu(ns, rep, hybrid, loss));
   const int64_t nch = (n_kept + kRowsPerChunk - 1) / kRowsPerChunk;
   const int64_t waves_per_wg = kIterBlock / kWave;
   int64_t g = std::min<int64_t>(int64_t(num_cu) * per_cu, (nch + waves_per_wg - 1) / waves_per_wg);
@@ -1098,10 +1153,13 @@ void launch_sgd_iter(const DevSgd& d, const DevPrepared& p, const SgdParams& sp,
   const int rep = u16 ? sgd_lds_rep(d.nl) : 0;
   const bool stats = sp.iteration == 1;
   const bool sample = sp.sample != 0;
-  if (stats && sample) launch_iter_t<true, true>(d, p, sp, u16, rep, grid, s);
-  else if (stats) launch_iter_t<true, false>(d, p, sp, u16, rep, grid, s);
-  else if (sample) launch_iter_t<false, true>(d, p, sp, u16, rep, grid, s);
-  else launch_iter_t<false, false>(d, p, sp, u16, rep, grid, s);
+#define TWTML_LOSS(L) \
+  if (stats && sample) launch_iter_t<L, true, true>(d, p, sp, u16, rep, grid, s); \
+  else if (stats) launch_iter_t<L, true, false>(d, p, sp, u16, rep, grid, s); \
+  else if (sample) launch_iter_t<L, false, true>(d, p, sp, u16, rep, grid, s); \
+  else launch_iter_t<L, false, false>(d, p, sp, u16, rep, grid, s)
+  if (sp.loss == kLossLogistic) { TWTML_LOSS(kLossLogistic); } else { TWTML_LOSS(kLossSquared); }
+#undef TWTML_LOSS
 }
 
 int sgd_partials(int64_t ns, bool u16, int grid) {
@@ -1332,7 +1390,7 @@ __global__ __launch_bounds__(kUpdThreads) void k_sgd_update(DevSgd d, SgdParams 
           }
           if (col >= kNumNumeric) mx = fmax(mx, fabs(double(float(wn))));   // the next iteration's weight scale
         } else if (col == ns) {
-          if (m > 0.0) d.loss_hist[it] = 0.5 * double(gi) * ldexp(1.0, -sL) / m;
+          if (m > 0.0) d.loss_hist[it] = (sp.loss == kLossLogistic ? 1.0 : 0.5) * double(gi) * ldexp(1.0, -sL) / m;
         }
       }
     }

@@ -52,7 +52,7 @@ from ..sources import make_source
 from ..utils.logging import setup_logging
 from ..utils.metrics import MetricsLogger
 
-__all__ = ["main", "build_engine", "LinearRegressionJob"]
+__all__ = ["main", "run_driver", "build_engine", "LinearRegressionJob"]
 
 # TWTML_SNAP_REUSE=0 (A/B): a fresh host array per checkpoint
 _SNAP_REUSE = os.environ.get("TWTML_SNAP_REUSE", "1") != "0"
@@ -69,8 +69,10 @@ DRIVER_RAW_SLOTS = DRIVER_PREFETCH_DEPTH + 2
 
 
 def build_engine(conf: ConfArguments, rank: int, world: int, device: Optional[int] = None,
-                 max_rows: int = 0):
-    """CPU (local[N]) or MI355X (rocm...) engine for this process."""
+                 max_rows: int = 0, loss: str = "squared"):
+    """CPU (local[N]) or MI355X (rocm...) engine for this process.
+    ``loss="logistic"``: the logistic-regression engines (labels from
+    ``conf.labelThreshold``, class threshold ``conf.threshold``)."""
     spec = conf.master_spec()
     F = conf.effectiveNumTextFeatures
     if spec.is_gpu:
@@ -94,7 +96,8 @@ def build_engine(conf: ConfArguments, rank: int, world: int, device: Optional[in
             return LRDeviceConfig(num_text_features=F, hash=conf.hash, step_size=conf.stepSize,
                                   num_iterations=conf.numIterations, fraction=conf.miniBatchFraction,
                                   begin=conf.numRetweetBegin, end=conf.numRetweetEnd,
-                                  max_rows=rows, max_units=rows * 290, ingest="utf8",
+                                  max_rows=rows, max_units=rows * 290, ingest="utf8", loss=loss,
+                                  label_threshold=conf.labelThreshold, threshold=conf.threshold,
                                   # device raw slots (TWTML_RAW_SLOTS overrides): the driver
                                   # prefetches only the batches its scheduler has sealed (at most
                                   # DRIVER_PREFETCH_DEPTH), so it never uses more than that + 2;
@@ -114,8 +117,18 @@ def build_engine(conf: ConfArguments, rank: int, world: int, device: Optional[in
         # batch one all-gather of the prep packets (overlapped with the
         # previous batch's GD loop) and the stats all-reduce
         comm = make_comm(dev, "rccl") if world > 1 else None
+        if loss == "logistic":
+            from ..ops.lr_engine import DeviceLogisticRegression
+            return DeviceLogisticRegression(cfg, device=dev, comm=comm)
         return DeviceLinearRegression(cfg, device=dev, comm=comm)
     from ..parallel.dist import allreduce_fn
+    if loss == "logistic":
+        from ..models.logistic_regression import CpuLogisticConfig, CpuLogisticRegression
+        lcfg = CpuLogisticConfig(num_text_features=F, hash=conf.hash, step_size=conf.stepSize,
+                                 num_iterations=conf.numIterations, fraction=conf.miniBatchFraction,
+                                 begin=conf.numRetweetBegin, end=conf.numRetweetEnd,
+                                 label_threshold=conf.labelThreshold, threshold=conf.threshold)
+        return CpuLogisticRegression(lcfg, allreduce=allreduce_fn(), rank=rank, world=world)
     cfg = CpuLRConfig(num_text_features=F, hash=conf.hash, step_size=conf.stepSize,
                       num_iterations=conf.numIterations, fraction=conf.miniBatchFraction,
                       begin=conf.numRetweetBegin, end=conf.numRetweetEnd)
@@ -285,10 +298,14 @@ class LinearRegressionJob:
                 # views of the engine's own host buffers: one write in flight at
                 # a time, so nothing else fetches before this save is done
                 size, idx, val = eng.snapshot_fetch(reuse=_SNAP_REUSE)
-                LinearRegressionModel.save_sparse(path, SparseWeights(size, idx, val), 0.0, prog)
+                self._save_model(path, SparseWeights(size, idx, val), prog)
             return save
         w = np.array(eng.get_weights(), dtype=np.float64, copy=True)
-        return lambda path, prog: LinearRegressionModel(w, 0.0).save(path, prog)
+        return lambda path, prog: self._save_model(path, w, prog)
+
+    def _save_model(self, path, weights, prog) -> None:
+        """Write the model directory (dense weights or ``SparseWeights``)."""
+        LinearRegressionModel.save_sparse(path, weights, 0.0, prog)
 
     def final_checkpoint(self) -> None:
         self.checkpointer.flush()
@@ -306,12 +323,19 @@ class LinearRegressionJob:
 
 
 def main(argv: Optional[List[str]] = None) -> int:
+    return run_driver(argv, APP_NAME, build_engine, LinearRegressionJob,
+                      lambda path: LinearRegressionModel.load(path).weights)
+
+
+def run_driver(argv: Optional[List[str]], app_name: str, make_engine, job_cls, load_weights) -> int:
+    """The streaming driver: ``make_engine(conf, rank, world)``, ``job_cls`` (a
+    :class:`LinearRegressionJob`) and ``load_weights(path)`` for ``--resume``."""
     setup_logging()
     exit_on_sigterm()
     from ..runtime.clock import streaming_clock
     args = load_java_opts(list(sys.argv[1:] if argv is None else argv))
     log.info("Parsing applications arguments")
-    conf = ConfArguments().setAppName(APP_NAME).parse(args)
+    conf = ConfArguments().setAppName(app_name).parse(args)
 
     from ..parallel.dist import init_distributed
     spec = conf.master_spec()
@@ -325,11 +349,11 @@ def main(argv: Optional[List[str]] = None) -> int:
 
     log.info("Initializing Spark Machine Learning Model...")
     MllibHelper.reset(conf)
-    engine = build_engine(conf, rank, world)
+    engine = make_engine(conf, rank, world)
     w0 = np.zeros(engine.num_weights)                      # Vectors.zeros(numFeatures)
     resume = load_resume_state(conf.resume, conf.checkpoint, rank)
     if resume.path:
-        w0 = LinearRegressionModel.load(resume.path).weights
+        w0 = load_weights(resume.path)
         log.info("resumed %d weights from %s (batch %d, %d records consumed)", w0.shape[0],
                  resume.path, resume.batches, resume.records)
     engine.set_weights(w0)
@@ -352,8 +376,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                                            shard=rank, num_shards=world,
                                            start=resume.records, batch_size=conf.batchSize)).cache()
     plot = broadcast_flag(session is not None and session.viz is not None)   # the same on every rank
-    job = LinearRegressionJob(conf, engine, session, rank,
-                              MetricsLogger(os.environ.get("TWTML_METRICS")), resume, world, plot=plot)
+    job = job_cls(conf, engine, session, rank,
+                  MetricsLogger(os.environ.get("TWTML_METRICS")), resume, world, plot=plot)
     log.info("Initializing prediction model...")
     stream.foreachRDD(job.on_batch)   # op #1 (stats) + op #2 (trainOn), prequential order
     if hasattr(engine, "prefetch"):   # device engine: H2D of queued batches overlaps training

@@ -6,6 +6,10 @@ micro-batch of ``--source synthetic|replay:FILE|twitter`` with it:
 ``engine.predict_batch(raw)``, the unfiltered fp64 predictions ``x . w`` of
 every tweet in record order (on ``rocm[N]`` one pass of ``csrc/hip/score.hip``
 per batch, on ``local[N]`` the fp64 CPU engine).  The model is never updated.
+A LogisticRegressionModel directory (the logistic driver's ``--checkpoint``) is
+scored as such: the output is chosen by the model class found in ``--model`` --
+the class (1.0 / 0.0) under the model's saved threshold, or the probability if
+the model was saved with its threshold cleared.
 
 ``--model DIR``       the model directory; its weight count must be
                       ``numTextFeatures + 4`` (``-f`` / ``--hash`` as trained)
@@ -48,8 +52,9 @@ APP_NAME = "twitter-stream-ml-score"
 class ScoreJob:
     """Per-batch logic of the scoring driver."""
 
-    def __init__(self, engine, out_dir: str = "", rank: int = 0, world: int = 1):
+    def __init__(self, engine, out_dir: str = "", rank: int = 0, world: int = 1, output: Optional[str] = None):
         self.engine = engine
+        self.output = output   # logistic models: "class" / "probability"; None: the engine's margin
         self.out_dir = out_dir
         self.suffix = f"_r{rank}" if world > 1 else ""
         self.batches = 0
@@ -62,7 +67,8 @@ class ScoreJob:
     def on_batch(self, rdd, time_ms: int) -> None:
         raw = rdd.raw
         t0 = time.perf_counter()
-        res = self.engine.predict_batch(raw, apply_filter=False)
+        kw = {} if self.output is None else {"output": self.output}
+        res = self.engine.predict_batch(raw, apply_filter=False, **kw)
         ms = (time.perf_counter() - t0) * 1e3
         pred = np.asarray(res["pred"], np.float64)
         seq = self.batches
@@ -95,8 +101,19 @@ def main(argv: Optional[List[str]] = None) -> int:
     if not conf.model:
         print("twtml-score: --model <MLlib model directory> is required", file=sys.stderr)
         return 2
+    output = None
     try:
-        w = LinearRegressionModel.load(conf.model).weights
+        from ..checkpoint.saveable import LOGISTIC_CLASS, model_class
+        logistic = model_class(conf.model) == LOGISTIC_CLASS
+        if logistic:
+            from ..models.logistic_regression import LogisticRegressionModel
+            m = LogisticRegressionModel.load(conf.model)
+            w = m.weights
+            output = "probability" if m.threshold is None else "class"
+            if m.threshold is not None:
+                conf.threshold = m.threshold   # the model's own threshold decides the class
+        else:
+            w = LinearRegressionModel.load(conf.model).weights
     except Exception as e:   # noqa: BLE001 -- any unreadable model is the same usage error
         print(f"twtml-score: cannot load the model at {conf.model}: {e}", file=sys.stderr)
         return 2
@@ -112,7 +129,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     MllibHelper.reset(conf)
     # every rank scores alone: an engine without a communicator, on its GPU
     dev = (spec.devices[rank] if spec.devices else rank) if spec.is_gpu else None
-    engine = build_engine(conf, 0, 1, device=dev)
+    engine = build_engine(conf, 0, 1, device=dev, loss="logistic" if logistic else "squared")
     engine.set_weights(w)
     log.info("scoring with %d weights from %s", w.shape[0], conf.model)
 
@@ -124,7 +141,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                            clock=streaming_clock())
     stream = ssc.twitterStream(make_source(conf.source, rate=conf.sourceRate, seed=conf.seed,
                                            shard=rank, num_shards=world, start=0, batch_size=conf.batchSize)).cache()
-    job = ScoreJob(engine, conf.predictOut, rank, world)
+    job = ScoreJob(engine, conf.predictOut, rank, world, output)
     stream.foreachRDD(job.on_batch)
     ssc.start()
     try:

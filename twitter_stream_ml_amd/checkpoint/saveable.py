@@ -43,9 +43,11 @@ import pyarrow as pa
 import pyarrow.parquet as pq
 
 __all__ = ["SparseWeights", "save_linear_regression", "load_linear_regression", "save_kmeans", "load_kmeans",
-           "LR_CLASS", "KMEANS_CLASS", "vector_udt_type"]
+           "save_logistic_regression", "load_logistic_regression", "model_class",
+           "LR_CLASS", "LOGISTIC_CLASS", "KMEANS_CLASS", "vector_udt_type"]
 
 LR_CLASS = "org.apache.spark.mllib.regression.LinearRegressionModel"
+LOGISTIC_CLASS = "org.apache.spark.mllib.classification.LogisticRegressionModel"
 KMEANS_CLASS = "org.apache.spark.mllib.clustering.KMeansModel"
 
 
@@ -243,6 +245,44 @@ def load_linear_regression(path: str) -> Tuple[np.ndarray, float]:
     if w.shape[0] != int(meta["numFeatures"]):
         raise ValueError(f"{path}: numFeatures {meta['numFeatures']} != {w.shape[0]}")
     return w, float(t.column("intercept")[0].as_py())
+
+
+def save_logistic_regression(path: str, weights, intercept: float = 0.0, threshold: Optional[float] = 0.5,
+                             progress: Optional[dict] = None) -> None:
+    """MLlib ``LogisticRegressionModel.save`` (``GLMClassificationModel.SaveLoadV1_0``): metadata
+    ``numFeatures`` / ``numClasses`` (binary: 2), one data row ``{weights, intercept, threshold}`` with a
+    null threshold after ``clearThreshold``.  ``weights``: a dense vector or :class:`SparseWeights`."""
+    w = weights if isinstance(weights, SparseWeights) else np.asarray(weights, dtype=np.float64)
+    size = w.size if isinstance(w, SparseWeights) else int(w.shape[0])
+    schema = pa.schema([pa.field("weights", vector_udt_type()), pa.field("intercept", pa.float64(), nullable=False),
+                        pa.field("threshold", pa.float64(), nullable=True)],
+                       metadata=_spark_row_metadata([("weights", "vector", True), ("intercept", "double", False),
+                                                     ("threshold", "double", True)]))
+    thr = pa.array([None if threshold is None else float(threshold)], pa.float64())
+    table = pa.Table.from_arrays([_udt_array([w]), pa.array([float(intercept)], pa.float64()), thr], schema=schema)
+    _write_dir(path, {"class": LOGISTIC_CLASS, "version": "1.0", "numFeatures": size, "numClasses": 2}, table,
+               {"progress.json": progress} if progress else None)
+
+
+def load_logistic_regression(path: str) -> Tuple[np.ndarray, float, Optional[float]]:
+    """``(weights, intercept, threshold or None)``."""
+    meta = _read_meta(path, LOGISTIC_CLASS)
+    if int(meta.get("numClasses", 2)) != 2:
+        raise ValueError(f"{path}: only binary models are supported, found numClasses {meta['numClasses']}")
+    t = _read_data(path)
+    if t.num_rows != 1:
+        raise ValueError(f"{path}: expected one data row, found {t.num_rows}")
+    w = _from_udt_column(t.column("weights"))[0]
+    if w.shape[0] != int(meta["numFeatures"]):
+        raise ValueError(f"{path}: numFeatures {meta['numFeatures']} != {w.shape[0]}")
+    thr = t.column("threshold")[0].as_py()
+    return w, float(t.column("intercept")[0].as_py()), (None if thr is None else float(thr))
+
+
+def model_class(path: str) -> str:
+    """The ``class`` of the model saved at ``path`` (its metadata line)."""
+    with open(os.path.join(path, "metadata", "part-00000")) as fh:
+        return str(json.loads(fh.readline()).get("class"))
 
 
 def save_kmeans(path: str, centers: np.ndarray, weights: Optional[np.ndarray] = None,

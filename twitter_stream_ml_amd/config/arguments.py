@@ -140,6 +140,9 @@ _EXT_FLAGS = {
     # apps/score.py (the training drivers ignore them)
     "--model": ("model", str),
     "--predictOut": ("predictOut", str),
+    # apps/logistic_regression.py (and apps/score.py with a logistic model)
+    "--labelThreshold": ("labelThreshold", int),
+    "--threshold": ("threshold", float),
 }
 
 _FLAG_LOOKUP = {}
@@ -199,6 +202,10 @@ class ConfArguments:
         self.checkReplicas = 0
         self.model = ""        # apps/score.py: MLlib model directory to score with
         self.predictOut = ""   # apps/score.py: directory of the per-batch prediction files
+        # apps/logistic_regression.py: label = retweetCount >= labelThreshold (-1: middle of the
+        # filter range), class 1 when the probability exceeds threshold
+        self.labelThreshold = c.getInt("labelThreshold") if c.hasPath("labelThreshold") else -1
+        self.threshold = c.getDouble("threshold") if c.hasPath("threshold") else 0.5
 
         self.usage = f"""
 Usage: python -m twitter_stream_ml_amd.apps.linear_regression
@@ -239,6 +246,9 @@ Usage: twtml-spark [options]
   --legacyNumTextFeatures                         reproduce the reference bug: ignore -f
   --model <dir>  --predictOut <dir>               scoring driver (apps.score / twtml-score): the MLlib
                                                   model directory to load, where predictions go
+  --labelThreshold <n>  --threshold <p>           logistic driver (apps.logistic_regression / twtml-logistic):
+                                                  class 1 is retweetCount >= n (default: middle of -B..-E);
+                                                  predicted class 1 when the probability exceeds p (0.5)
   """
 
         if get_property("SPARK_SUBMIT") != "true":

@@ -29,7 +29,7 @@ from ..records.batch import RETWEET_COUNT, RawBatch, Utf8Text
 from ._native import hip, host
 from .ingest import SlotPipeline
 
-__all__ = ["LRDeviceConfig", "DeviceLinearRegression", "prelower", "HostBatchView", "register_host",
+__all__ = ["LRDeviceConfig", "DeviceLinearRegression", "DeviceLogisticRegression", "prelower", "HostBatchView", "register_host",
            "unregister_host", "Utf8Text", "encode_utf8"]
 
 
@@ -101,6 +101,19 @@ class LRDeviceConfig:
     # the cost of queueing latency (profiles/r6/raw_slots_sweep.txt: 6 is
     # the knee of tweets/s vs p50 on the headline bench).
     raw_slots: int = 0
+    # GD loss: "squared" (StreamingLinearRegressionWithSGD, LeastSquaresGradient)
+    # or "logistic" (StreamingLogisticRegressionWithSGD, binary LogisticGradient;
+    # csrc/hip/sgd.hip LOSS).  Logistic: the label is retweetCount >=
+    # label_threshold (< 0: the middle of begin..end), the prequential
+    # prediction the class probability > threshold.
+    loss: str = "squared"
+    label_threshold: int = -1
+    threshold: float = 0.5
+
+    def effective_label_threshold(self) -> int:
+        if self.loss == "logistic" and self.label_threshold < 0:
+            return (int(self.begin) + int(self.end)) // 2
+        return int(self.label_threshold)
 
     def as_dict(self) -> Dict[str, object]:
         return {
@@ -124,8 +137,15 @@ class LRDeviceConfig:
             "overlap": int(bool(self.overlap)),
             "force_dp": int(bool(self.force_dp)),
             "comm_timing": int(bool(self.comm_timing)),
+            "loss": _LOSSES[self.loss],
+            "label_threshold": self.effective_label_threshold(),
+            "threshold": float(self.threshold),
             **raw_slots_entry(self.raw_slots),
         }
+
+
+_LOSSES = {"squared": 0, "logistic": 1}      # kLossSquared / kLossLogistic (csrc/hip/kernels.h)
+_LINKS = {"margin": 0, "probability": 1, "class": 2}   # kLink* (csrc/hip/kernels.h)
 
 
 def raw_slots_entry(n: int) -> Dict[str, int]:
@@ -323,6 +343,8 @@ class DeviceLinearRegression:
     """StreamingLinearRegressionWithSGD state + pipeline on one GPU."""
 
     def __init__(self, cfg: LRDeviceConfig, device: int = 0, comm=None):
+        if cfg.loss not in _LOSSES:
+            raise ValueError(f"unknown loss {cfg.loss!r} (squared or logistic)")
         self.cfg = cfg
         self.device = int(device)
         self.comm = comm
@@ -391,16 +413,20 @@ class DeviceLinearRegression:
 
     # ---- inference (csrc/hip/score.hip) -----------------------------------
     def predict_batch(self, raw: RawBatch, apply_filter: bool = False,
-                      now_ms: Optional[int] = None) -> Dict[str, object]:
+                      now_ms: Optional[int] = None, output: str = "margin") -> Dict[str, object]:
         """Score one raw micro-batch with the current weights, without
         training on it: ``rows`` (int64 raw row ids, ascending) and ``pred``
         (their fp64 predictions ``x . w``, nothing rounded; arrays owned by the
         caller), ``n_raw``, ``n_scored``, ``score_ms`` (device time of the
         scoring kernels).  ``apply_filter``: only the rows the training filter
-        keeps.  The batch is staged into a raw slot the training pipeline
+        keeps.  ``output``: ``"margin"`` (``x . w``), ``"probability"`` (``1 /
+        (1 + exp(-margin))``) or ``"class"`` (margin > logit(``cfg.threshold``)
+        as 1.0 / 0.0), applied per row on the device in fp64.  The batch is staged into a raw slot the training pipeline
         holds no batch in and never enters the engine's prepare-ahead queue;
         the model, the prefetched batches and a pending snapshot are left as
         they are.  Call it from the thread that calls ``train_batch``."""
+        if output not in _LINKS:
+            raise ValueError(f"unknown output {output!r} (class, probability or margin)")
         self.staging(0)._check(raw)   # the ValueError of training, before a slot is touched
         if raw.n == 0:                # nothing is staged or launched
             return {"n_raw": 0, "n_scored": 0, "rows": np.zeros(0, np.int64), "pred": np.zeros(0, np.float64),
@@ -411,7 +437,7 @@ class DeviceLinearRegression:
             self._eng.submit(hb._hb, int(hb.n), int(hb.bytes), int(slot), int(hb.ext_text),
                              int(hb.batch_time_ms), False)
             return self._eng.score(int(slot), int(raw.batch_time_ms if now_ms is None else now_ms),
-                                   bool(apply_filter))
+                                   bool(apply_filter), _LINKS[output])
         finally:
             self._pipe.score_done(slot)
 
@@ -422,6 +448,23 @@ class DeviceLinearRegression:
 
     def synchronize(self) -> None:
         self._eng.synchronize()
+
+
+class DeviceLogisticRegression(DeviceLinearRegression):
+    """StreamingLogisticRegressionWithSGD on one GPU: the LR engine with
+    ``loss="logistic"`` -- 0/1 labels (``retweetCount >= label_threshold``),
+    the logistic row epilogue in the iteration kernels, class predictions in
+    the prequential statistics -- and ``predict_batch`` defaulting to the
+    class."""
+
+    def __init__(self, cfg: LRDeviceConfig, device: int = 0, comm=None):
+        if cfg.loss != "logistic":
+            raise ValueError('DeviceLogisticRegression needs LRDeviceConfig(loss="logistic")')
+        super().__init__(cfg, device, comm)
+
+    def predict_batch(self, raw: RawBatch, apply_filter: bool = False,
+                      now_ms: Optional[int] = None, output: str = "class") -> Dict[str, object]:
+        return super().predict_batch(raw, apply_filter, now_ms, output)
 
 
 def batch_report(res: Dict[str, object]) -> Dict[str, float]:
