@@ -1494,6 +1494,172 @@ void launch_km_cluster_sums(const float* X, const int64_t* mx, const int32_t* la
                        dp, km_cols_pow2(d), sums);
 }
 
+// ---------------------------------------------------------------------------
+// Scoring (KMeansModel.computeCost): the squared distance of every scored row
+// to its assigned centre, fp64 against the master centres (k_km_refine's
+// expression, nothing rounded to fp32), their sum and the rows per cluster.
+//
+// A row's bits depend on the row alone: LPR lanes per row, fixed by dp; lane
+// l sums its contiguous columns in column order (explicit fma, so no
+// contraction choice is left to the compiler) and the lanes combine in a
+// fixed xor-shuffle tree.  dp <= 128: lane l owns the 16 bytes [4 l, 4 l + 4)
+// of the row (one dwordx4 per lane, the row's lanes coalesced; dp == 2: one
+// lane, 8 bytes).  Wider rows (dp == d, unpadded and unaligned): one wave per
+// row, lane l the columns [l c, (l + 1) c), c = ceil(d / 64).
+//
+// A workgroup takes kKmCostIters groups of 4 x (64 / LPR) consecutive rows;
+// a row's leader lane adds its rows' distances in row order, the wave reduces
+// in the fixed tree, thread 0 adds the 4 wave sums in wave order: one partial
+// per workgroup.  k_km_cost_final (one workgroup) adds each thread's
+// contiguous run of partials in index order, then a fixed LDS tree.  The
+// order depends only on n and dp: two calls on a batch give the same bits.
+// ---------------------------------------------------------------------------
+constexpr int kKmCostIters = 8;
+constexpr int kKmCostWaves = kBlock / kWave;
+
+KmCostShape km_cost_shape(int dp) {
+  const int lpr = dp > 128 ? kWave : (dp >= 4 ? dp / 4 : 1);
+  return {lpr, kWave / lpr, kKmCostWaves * (kWave / lpr) * kKmCostIters};
+}
+
+// (a model with NaN centres can leave the index of a padded centre, >= k)
+__device__ __forceinline__ int km_cost_label(int lab, int k) { return lab < 0 ? 0 : (lab < k ? lab : k - 1); }
+
+template <int LPR, int W>   // lanes per row, columns per lane (0: a run of ceil(d / 64), any width)
+__global__ __launch_bounds__(kBlock) void k_km_cost(const float* X, const double* fac, const int32_t* labels,
+                                                    const double* centers, int64_t n, int k, int d, int dp,
+                                                    double* dist2, double* partials) {
+  constexpr int RPW = kWave / LPR;
+  __shared__ double wsum[kKmCostWaves];
+  const int lane = lane_id(), w = threadIdx.x / kWave;
+  const int sub = lane / LPR, l = lane % LPR;
+  const int64_t base = int64_t(blockIdx.x) * (kKmCostWaves * RPW * kKmCostIters);
+  double acc = 0.0;
+  if constexpr (W > 0) {
+    using vec = __attribute__((ext_vector_type(W))) float;
+    const int j0 = W * l;            // j0 + W <= dp
+    double f[W];
+#pragma unroll
+    for (int q = 0; q < W; ++q) f[q] = fac[j0 + q];
+    vec x[kKmCostIters];
+    int lab[kKmCostIters];
+#pragma unroll
+    for (int it = 0; it < kKmCostIters; ++it) {   // all loads of the workgroup's rows in flight first
+      const int64_t p = base + int64_t(it * kKmCostWaves + w) * RPW + sub;
+      x[it] = vec{};
+      lab[it] = 0;
+      if (p < n) {
+        x[it] = *reinterpret_cast<const vec*>(X + p * dp + j0);
+        lab[it] = km_cost_label(labels[p], k);
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < kKmCostIters; ++it) {
+      const int64_t p = base + int64_t(it * kKmCostWaves + w) * RPW + sub;
+      const double* c = centers + int64_t(lab[it]) * d + j0;
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < W; ++q)
+        if (p < n && j0 + q < d) {   // (pad columns have no centre entry)
+          const double t = fma(double(x[it][q]), f[q], -c[q]);
+          s = fma(t, t, s);
+        }
+#pragma unroll
+      for (int off = LPR / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
+      if (l == 0 && p < n) {
+        dist2[p] = s;
+        acc += s;
+      }
+    }
+  } else {
+    const int cpl = (d + kWave - 1) / kWave;
+    const int j0 = lane * cpl < d ? lane * cpl : d;
+    const int j1 = j0 + cpl < d ? j0 + cpl : d;
+#pragma unroll 1
+    for (int it = 0; it < kKmCostIters; ++it) {
+      const int64_t p = base + int64_t(it * kKmCostWaves + w) * RPW + sub;
+      if (p >= n) break;             // wave-uniform: one row per wave
+      const float* x = X + p * dp;
+      const double* c = centers + int64_t(km_cost_label(labels[p], k)) * d;
+      double s = 0.0;
+      for (int j = j0; j < j1; ++j) {
+        const double t = fma(double(x[j]), fac[j], -c[j]);
+        s = fma(t, t, s);
+      }
+#pragma unroll
+      for (int off = LPR / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
+      if (l == 0) {
+        dist2[p] = s;
+        acc += s;
+      }
+    }
+  }
+  // (lanes that lead no row hold 0)
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+  if (lane == 0) wsum[w] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = wsum[0];
+#pragma unroll
+    for (int i = 1; i < kKmCostWaves; ++i) t += wsum[i];
+    partials[blockIdx.x] = t;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_km_cost_final(const double* partials, int np, double* cost) {
+  __shared__ double red[kBlock];
+  const int run = (np + kBlock - 1) / kBlock;
+  const int i0 = int(threadIdx.x) * run < np ? int(threadIdx.x) * run : np;
+  const int i1 = i0 + run < np ? i0 + run : np;
+  double t = 0.0;
+  for (int i = i0; i < i1; ++i) t += partials[i];
+  red[threadIdx.x] = t;
+  __syncthreads();
+  for (int st = kBlock / 2; st > 0; st >>= 1) {
+    if (int(threadIdx.x) < st) red[threadIdx.x] += red[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) cost[0] = red[0];
+}
+
+void launch_km_cost(const float* X, const double* f64, const int32_t* labels, const double* centers,
+                    const int64_t* counters, int64_t n, int k, int d, int dp, double* dist2,
+                    double* partials, double* cost, int64_t* sizes, hipStream_t s) {
+  if (n <= 0) throw std::invalid_argument("launch_km_cost: no rows");
+  const KmCostShape sh = km_cost_shape(dp);
+  const int np = ceil_div(n, sh.rows_per_wg);
+#define KM_COST(LPRV, WV)                                                                          \
+  TWTML_LAUNCH((k_km_cost<LPRV, WV>), dim3(np), dim3(kBlock), 0, s, X, f64, labels, centers, n, k, \
+                     d, dp, dist2, partials)
+  switch (dp) {
+    case 2: KM_COST(1, 2); break;
+    case 4: KM_COST(1, 4); break;
+    case 8: KM_COST(2, 4); break;
+    case 16: KM_COST(4, 4); break;
+    case 32: KM_COST(8, 4); break;
+    case 64: KM_COST(16, 4); break;
+    case 128: KM_COST(32, 4); break;
+    default:
+      if (dp <= 128) throw std::invalid_argument("launch_km_cost: dp is not a padded width");
+      KM_COST(kWave, 0);
+  }
+#undef KM_COST
+  TWTML_LAUNCH(k_km_cost_final, dim3(1), dim3(kBlock), 0, s, partials, np, cost);
+  // rows per cluster: integer atomics, exact in any order
+  TWTML_HIP_CHECK(hipMemsetAsync(sizes, 0, sizeof(int64_t) * size_t(k), s));
+  if (k <= kKmLdsBins) {
+    int grid = int((n + kKmChunk - 1) / kKmChunk);
+    grid = grid > 1024 ? 1024 : grid;
+    TWTML_LAUNCH(k_km_label_hist, dim3(grid), dim3(kBlock), sizeof(uint32_t) * size_t(k), s, labels,
+                       counters, k, sizes);
+  } else {
+    int grid = int(n / kBlock + 1);
+    if (grid > 4096) grid = 4096;
+    TWTML_LAUNCH(k_km_label_hist_g, dim3(grid), dim3(kBlock), 0, s, labels, counters, sizes);
+  }
+}
+
 // the all-reduced integer sums -> the fp64 sums of the SCALED features
 // (factor_j 2^s_j sum q) and the counts the update reads
 __global__ void k_km_sums_f64(const int64_t* si, const int64_t* mx, const double* fac, int k, int d,

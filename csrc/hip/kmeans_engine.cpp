@@ -1,5 +1,6 @@
 // KMEngine: the streaming k-means micro-batch pipeline (see kmeans.hip).
 #include "kmeans_engine.h"
+#include "../common/task_pool.h"
 #include "trace.h"
 
 #include <pybind11/numpy.h>
@@ -10,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <stdexcept>
 
 #include "kmeans_kernels.h"
@@ -92,6 +94,139 @@ void KMEngine::submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, c
   raw_.submit(hb, n, bytes, slot, copy_, 2, ext_text);
 }
 
+// K11 scaler, exact: the column max (all-reduced MAX) fixes every column's
+// quantization shift, then n and the integer column sums (all-reduced SUM);
+// both are the same bits on every rank and in any summation order
+void KMEngine::fit_moments(bool reduce, hipStream_t s) {
+  const int d = d_;
+  int64_t* mx = qmom_;
+  int64_t* mq = qmom_ + d;
+  TWTML_HIP_CHECK(hipMemsetAsync(qmom_, 0, sizeof(int64_t) * size_t(d + 1 + 4 * d), s));
+  launch_km_colmax(X_, prep_.counters, d, dp_, mx, cfg_.max_rows, s);
+  if (reduce) comm_->allreduce(mx, size_t(d), ncclInt64, ncclMax, s);
+  launch_km_moments_q(X_, prep_.counters, d, dp_, mx, mq, cfg_.max_rows, s);
+  if (reduce) comm_->allreduce(mq, size_t(1 + 4 * d), ncclInt64, ncclSum, s);
+  TWTML_HIP_CHECK(hipMemcpyAsync(host_q_, qmom_, sizeof(int64_t) * size_t(d + 1 + 4 * d), hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipMemcpyAsync(host_out_ + 1, prep_.counters, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// batch: std_j = sqrt(M2_j / (n - 1)) (n < 2 -> 0), M2 = (n sum q^2 - (sum q)^2) / n
+// in 128-bit integers; given: the caller's std_j; either way factor_j =
+// std_j != 0 ? 1 / std_j : 0 (StandardScalerModel.transform); none: factor 1
+void KMEngine::upload_factors(int mode, int64_t n, const double* given, std::vector<double>& std,
+                              hipStream_t s) {
+  const int d = d_;
+  double* f64 = static_cast<double*>(host_fac_.get());
+  float* f32 = reinterpret_cast<float*>(f64 + dp_);
+  if (mode != kKmScalerNone) std.assign(size_t(d), 0.0);
+  for (int j = 0; j < dp_; ++j) {
+    double f = 0.0;
+    if (j < d) {
+      if (mode == kKmScalerBatch) {
+        const int64_t* m = host_q_ + d + 1 + 4 * j;
+        const __int128 s2 = (__int128(m[1]) << 32) + (__int128(m[2]) << 16) + __int128(m[3]);
+        const __int128 num = __int128(n) * s2 - __int128(m[0]) * __int128(m[0]);
+        double sd = 0.0;
+        if (n > 1 && num > 0) {
+          const long double var = std::ldexp(static_cast<long double>(num), 2 * km_quant_shift(host_q_[j])) /
+                                  (static_cast<long double>(n) * static_cast<long double>(n - 1));
+          sd = std::sqrt(static_cast<double>(var));
+        }
+        std[size_t(j)] = sd;
+        f = sd != 0.0 ? 1.0 / sd : 0.0;
+      } else if (mode == kKmScalerGiven) {
+        const double sd = given[j];
+        std[size_t(j)] = sd;
+        f = sd != 0.0 ? 1.0 / sd : 0.0;
+      } else {
+        f = 1.0;
+      }
+    }
+    f64[j] = f;
+    f32[j] = float(f);
+  }
+  TWTML_HIP_CHECK(hipMemcpyAsync(fac64_, f64, sizeof(double) * size_t(dp_), hipMemcpyHostToDevice, s));
+  TWTML_HIP_CHECK(hipMemcpyAsync(fac32_, f32, sizeof(float) * size_t(dp_), hipMemcpyHostToDevice, s));
+}
+
+void KMEngine::ensure_score() {
+  if (dist2_) return;
+  const size_t R = size_t(cfg_.max_rows);
+  cost_parts_ = R / size_t(km_cost_shape(dp_).rows_per_wg) + 1;
+  dist2_ = arena_.alloc<double>(R);
+  cost_part_ = arena_.alloc<double>(cost_parts_ + 1);
+  score_host_.alloc(R * (sizeof(int64_t) + sizeof(double) + sizeof(int32_t)) + sizeof(double) +
+                        sizeof(int64_t) * size_t(cfg_.k),
+                    hipHostMallocDefault);
+}
+
+KMScoreResult KMEngine::score(int slot, bool apply_filter, int scaler_mode, const double* std) {
+  if (scaler_mode < kKmScalerBatch || scaler_mode > kKmScalerNone)
+    throw std::invalid_argument("score(): unknown scaler mode");
+  if (scaler_mode == kKmScalerGiven && !std) throw std::invalid_argument("score(): the given scaler needs std");
+  TraceRange tr("twtml.km.score");
+  TWTML_HIP_CHECK(hipSetDevice(device_));
+  hipStream_t s = compute_;
+  const int k = cfg_.k, d = d_;
+  ensure_score();
+  KMScoreResult res;
+  res.sizes.assign(size_t(k), 0);
+  const DevRawBatch b = raw_.acquire(slot, s);
+  res.n_raw = b.n;
+  TWTML_HIP_CHECK(hipEventRecord(ev0_, s));
+  FeaturizeParams fp{1, 0, apply_filter ? 1 : 0, 0, 0, 0, 0};   // the training filter, or every row
+  TWTML_HIP_CHECK(hipMemsetAsync(prep_.counters, 0, 8 * sizeof(int64_t), s));
+  launch_filter_only(b, prep_, fp, s);
+  launch_km_features(b, prep_.kept, prep_.counters, X_, dp_, cfg_.text_dims, lower_page_,
+                     lower_blocks_, cfg_.max_rows, s);
+  raw_.release_slot(slot, s);
+  if (scaler_mode == kKmScalerBatch) {
+    fit_moments(false, s);   // never a collective: a DP rank fits on its own shard
+  } else {
+    TWTML_HIP_CHECK(hipMemcpyAsync(host_out_ + 1, prep_.counters, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    TWTML_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  int64_t n;
+  std::memcpy(&n, host_out_ + 1, sizeof(int64_t));
+  if (n < 0 || n > b.n || n > cfg_.max_rows || (!apply_filter && n != b.n))
+    throw std::runtime_error("score(): kept-row count out of range");
+  res.n_scored = n;
+  if (n == 0) {   // nothing to assign: no assign or cost launch
+    TWTML_HIP_CHECK(hipEventRecord(ev1_, s));
+    TWTML_HIP_CHECK(hipStreamSynchronize(s));
+    TWTML_HIP_CHECK(hipEventElapsedTime(&res.ms, ev0_, ev1_));
+    return res;
+  }
+  upload_factors(scaler_mode, n, std, res.std, s);
+  auto* refine_cnt = reinterpret_cast<unsigned long long*>(prep_.counters + 5);
+  launch_km_assign(X_, fac32_, fac64_, prep_.counters, c32_, cnorm_, centers_, k, d, dp_, labels_,
+                   refine_, refine_cnt, frag_, cnp_, cfg_.max_rows, cfg_.mfma != 0, cfg_.mfma == 1, s);
+  double* cost = cost_part_ + cost_parts_;
+  launch_km_cost(X_, fac64_, labels_, centers_, prep_.counters, n, k, d, dp_, dist2_, cost_part_, cost,
+                 lhist_, s);
+  TWTML_HIP_CHECK(hipEventRecord(ev1_, s));
+  const size_t R = size_t(cfg_.max_rows), un = size_t(n);
+  auto* h_rows = static_cast<int64_t*>(score_host_.get());
+  auto* h_dist2 = reinterpret_cast<double*>(h_rows + R);
+  double* h_cost = h_dist2 + R;
+  auto* h_sizes = reinterpret_cast<int64_t*>(h_cost + 1);
+  auto* h_labels = reinterpret_cast<int32_t*>(h_sizes + k);
+  TWTML_HIP_CHECK(hipMemcpyAsync(h_rows, prep_.kept, sizeof(int64_t) * un, hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipMemcpyAsync(h_dist2, dist2_, sizeof(double) * un, hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipMemcpyAsync(h_cost, cost, sizeof(double), hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipMemcpyAsync(h_sizes, lhist_, sizeof(int64_t) * size_t(k), hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipMemcpyAsync(h_labels, labels_, sizeof(int32_t) * un, hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipStreamSynchronize(s));
+  res.rows = h_rows;
+  res.dist2 = h_dist2;
+  res.labels = h_labels;
+  res.cost = *h_cost;
+  res.sizes.assign(h_sizes, h_sizes + k);
+  TWTML_HIP_CHECK(hipEventElapsedTime(&res.ms, ev0_, ev1_));
+  return res;
+}
+
 KMResult KMEngine::process(int slot, bool want_labels) {
   TraceRange tr("twtml.km.batch");
   TWTML_HIP_CHECK(hipSetDevice(device_));
@@ -107,19 +242,8 @@ KMResult KMEngine::process(int slot, bool want_labels) {
   launch_km_features(b, prep_.kept, prep_.counters, X_, dp_, cfg_.text_dims, lower_page_,
                      lower_blocks_, cfg_.max_rows, s);
   raw_.release_slot(slot, s);
-  // K11 scaler, exact: the column max (all-reduced MAX) fixes every column's
-  // quantization shift, then n and the integer column sums (all-reduced SUM);
-  // both are the same bits on every rank and in any summation order
   int64_t* mx = qmom_;
-  int64_t* mq = qmom_ + d;
-  TWTML_HIP_CHECK(hipMemsetAsync(qmom_, 0, sizeof(int64_t) * size_t(d + 1 + 4 * d), s));
-  launch_km_colmax(X_, prep_.counters, d, dp_, mx, cfg_.max_rows, s);
-  if (dist_) comm_->allreduce(mx, size_t(d), ncclInt64, ncclMax, s);
-  launch_km_moments_q(X_, prep_.counters, d, dp_, mx, mq, cfg_.max_rows, s);
-  if (dist_) comm_->allreduce(mq, size_t(1 + 4 * d), ncclInt64, ncclSum, s);
-  TWTML_HIP_CHECK(hipMemcpyAsync(host_q_, qmom_, sizeof(int64_t) * size_t(d + 1 + 4 * d), hipMemcpyDeviceToHost, s));
-  TWTML_HIP_CHECK(hipMemcpyAsync(host_out_ + 1, prep_.counters, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  TWTML_HIP_CHECK(hipStreamSynchronize(s));
+  fit_moments(dist_, s);
   res.n_global = host_q_[d];
   int64_t nl;
   std::memcpy(&nl, host_out_ + 1, sizeof(int64_t));
@@ -129,37 +253,7 @@ KMResult KMEngine::process(int slot, bool want_labels) {
     TWTML_HIP_CHECK(hipStreamSynchronize(s));
     return res;
   }
-  // std_j = sqrt(M2_j / (n - 1)) (n < 2 -> 0); factor_j = std_j != 0 ? 1 / std_j : 0
-  // (StandardScalerModel.transform), M2 = (n sum q^2 - (sum q)^2) / n in
-  // 128-bit integers; scale == 0 -> factor 1
-  double* f64 = static_cast<double*>(host_fac_.get());
-  float* f32 = reinterpret_cast<float*>(f64 + dp_);
-  if (cfg_.scale) res.std.assign(size_t(d), 0.0);
-  for (int j = 0; j < dp_; ++j) {
-    double f = 0.0;
-    if (j < d) {
-      if (cfg_.scale) {
-        const int64_t n = res.n_global;
-        const int64_t* m = host_q_ + d + 1 + 4 * j;
-        const __int128 s2 = (__int128(m[1]) << 32) + (__int128(m[2]) << 16) + __int128(m[3]);
-        const __int128 num = __int128(n) * s2 - __int128(m[0]) * __int128(m[0]);
-        double sd = 0.0;
-        if (n > 1 && num > 0) {
-          const long double var = std::ldexp(static_cast<long double>(num), 2 * km_quant_shift(host_q_[j])) /
-                                  (static_cast<long double>(n) * static_cast<long double>(n - 1));
-          sd = std::sqrt(static_cast<double>(var));
-        }
-        res.std[size_t(j)] = sd;
-        f = sd != 0.0 ? 1.0 / sd : 0.0;
-      } else {
-        f = 1.0;
-      }
-    }
-    f64[j] = f;
-    f32[j] = float(f);
-  }
-  TWTML_HIP_CHECK(hipMemcpyAsync(fac64_, f64, sizeof(double) * size_t(dp_), hipMemcpyHostToDevice, s));
-  TWTML_HIP_CHECK(hipMemcpyAsync(fac32_, f32, sizeof(float) * size_t(dp_), hipMemcpyHostToDevice, s));
+  upload_factors(cfg_.scale ? kKmScalerBatch : kKmScalerNone, res.n_global, nullptr, res.std, s);
   // K8 assignment with the current centres, K9 sums, K10 update.  The
   // near-tie lists in refine_, their counts in counters[5..6].
   auto* refine_cnt = reinterpret_cast<unsigned long long*>(prep_.counters + 5);
@@ -288,6 +382,57 @@ void bind_kmeans(py::module_& m) {
           out["pred"] = py::none();
         return out;
       }, py::arg("slot"), py::arg("want_labels") = false)
+      .def("score", [](KMEngine& e, int slot, bool apply_filter, int scaler_mode,
+                       std::optional<py::array_t<double, py::array::c_style | py::array::forcecast>> std) {
+        if (scaler_mode == kKmScalerGiven && (!std || std->size() != e.d()))
+          throw std::invalid_argument("score(): the given scaler needs d stds");
+        KMScoreResult r;
+        {
+          const double* sp = std ? std->data() : nullptr;
+          py::gil_scoped_release nogil;
+          r = e.score(slot, apply_filter, scaler_mode, sp);
+        }
+        // copies owned by the caller (the engine's pinned buffer is reused)
+        py::array_t<int64_t> rows(r.n_scored);
+        py::array_t<int32_t> pred(r.n_scored);
+        py::array_t<double> dist2(r.n_scored);
+        if (r.n_scored > 0) {
+          // 1 MB pieces on the host pool: a fresh array's first-touch page
+          // faults make one thread's copy of 20 B x 1M rows longer than the kernels
+          struct Part { char* dst; const char* src; size_t bytes; };
+          const size_t n = size_t(r.n_scored);
+          const Part parts[3] = {{reinterpret_cast<char*>(rows.mutable_data()), reinterpret_cast<const char*>(r.rows), 8 * n},
+                                 {reinterpret_cast<char*>(dist2.mutable_data()), reinterpret_cast<const char*>(r.dist2), 8 * n},
+                                 {reinterpret_cast<char*>(pred.mutable_data()), reinterpret_cast<const char*>(r.labels), 4 * n}};
+          constexpr size_t kPiece = size_t(1) << 20;
+          int first[4] = {0, 0, 0, 0};
+          for (int p = 0; p < 3; ++p) first[p + 1] = first[p] + int((parts[p].bytes + kPiece - 1) / kPiece);
+          py::gil_scoped_release nogil;
+          TaskPool::get().run(first[3], [&](int t) {
+            const int p = t >= first[2] ? 2 : (t >= first[1] ? 1 : 0);
+            const size_t off = size_t(t - first[p]) * kPiece;
+            std::memcpy(parts[p].dst + off, parts[p].src + off, std::min(kPiece, parts[p].bytes - off));
+          });
+        }
+        py::dict out;
+        out["n_raw"] = r.n_raw;
+        out["n_scored"] = r.n_scored;
+        out["rows"] = rows;
+        out["pred"] = pred;
+        out["dist2"] = dist2;
+        out["cost"] = r.cost;
+        out["sizes"] = py::array_t<int64_t>(py::ssize_t(r.sizes.size()), r.sizes.data());
+        out["std"] = py::array_t<double>(py::ssize_t(r.std.size()), r.std.data());
+        out["score_ms"] = r.ms;
+        return out;
+      }, py::arg("slot"), py::arg("apply_filter") = true, py::arg("scaler_mode") = 0, py::arg("std") = py::none(),
+         "inference only: labels, squared distances, cost and cluster sizes of the batch in `slot` under the "
+         "current model; scaler_mode 0 per-batch fit, 1 the given std[d], 2 none")
+      .def_static("cost_shape", [](int dp) {
+        const KmCostShape sh = km_cost_shape(dp);
+        return py::make_tuple(sh.lanes_per_row, sh.rows_per_wave, sh.rows_per_wg);
+      }, py::arg("dp"), "the cost kernel's (lanes per row, rows per wave, rows per workgroup) at padded width dp")
+      .def_property_readonly("dp", &KMEngine::dp)
       .def("set_state", [](KMEngine& e, py::array_t<double, py::array::c_style | py::array::forcecast> c,
                            py::array_t<double, py::array::c_style | py::array::forcecast> w) {
         if (c.size() != py::ssize_t(e.k()) * e.d() || w.size() != e.k())

@@ -36,12 +36,37 @@ struct KMResult {
   float ms = 0.f;
 };
 
+// score(): how the scaler factors are chosen
+constexpr int kKmScalerBatch = 0;   // StandardScaler fitted on the scored rows (as training, no collective)
+constexpr int kKmScalerGiven = 1;   // the caller's std[d]: factor_j = std_j != 0 ? 1 / std_j : 0
+constexpr int kKmScalerNone = 2;    // factor 1
+
+// The arrays point into the engine's pinned buffer: valid until the next score().
+struct KMScoreResult {
+  int64_t n_raw = 0, n_scored = 0;
+  const int64_t* rows = nullptr;    // [n_scored] raw row ids, ascending
+  const int32_t* labels = nullptr;  // [n_scored] closest centre
+  const double* dist2 = nullptr;    // [n_scored] squared distance to it, in the scaled space
+  double cost = 0.0;                // sum of dist2 (KMeansModel.computeCost), summed on the device
+  std::vector<int64_t> sizes;       // [k] rows per cluster
+  std::vector<double> std;          // [d] column stds used (empty: no scaler)
+  float ms = 0.f;                   // device time of the kernels (events)
+};
+
 class KMEngine {
  public:
   KMEngine(int device, const KMConfig& cfg, std::shared_ptr<Comm> comm);
   ~KMEngine();
   void submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, const uint8_t* ext_text = nullptr);
   KMResult process(int slot, bool want_labels);
+  // Inference only: clusters and cost of the batch in `slot` under the current
+  // model.  Filter (apply_filter: the training filter, else every row),
+  // features, scaler factors by `scaler_mode` (std: kKmScalerGiven's d
+  // values), the training assignment with its fp64 near-tie refine, then the
+  // fp64 cost pass.  Leaves the model, the other raw slots and the
+  // communicator untouched; reuses the batch scratch of process() (both end in
+  // a stream sync, so they never overlap).
+  KMScoreResult score(int slot, bool apply_filter, int scaler_mode, const double* std);
   // Forget a submitted batch that will not be processed: waits for its H2D
   // (the staging buffer may then be rewritten); the copy stream keeps the
   // slot's next H2D in order behind it.
@@ -49,9 +74,11 @@ class KMEngine {
   void set_state(const double* centers, const double* weights);
   void get_state(double* centers, double* weights) const;
   // Debug/test: the labels left by the last process() (the update's
-  // assignment with the old centres when want_labels was false).
+  // assignment with the old centres when want_labels was false) or score(),
+  // whichever ran last.
   std::vector<int32_t> debug_labels() const;
-  // Debug/test: the unscaled fp32 feature rows [n_local][dp] of the last batch.
+  // Debug/test: the unscaled fp32 feature rows [n_local][dp] of the last
+  // batch, processed or scored.
   std::vector<float> debug_features() const;
   int k() const { return cfg_.k; }
   int d() const { return d_; }
@@ -61,6 +88,13 @@ class KMEngine {
   void synchronize();
 
  private:
+  // Exact integer column moments of X_ (kmeans.hip K11) on the host: qmom_ ->
+  // host_q_, the kept-row count -> host_out_ + 1; syncs `s`.
+  void fit_moments(bool reduce, hipStream_t s);
+  // Host factors -> fac64_ / fac32_ by scaler mode (batch: from host_q_ and
+  // the n rows fitted); `std` receives the d stds used (none: empty).
+  void upload_factors(int mode, int64_t n, const double* given, std::vector<double>& std, hipStream_t s);
+  void ensure_score();
   int device_;
   KMConfig cfg_;
   int d_, dp_;
@@ -88,6 +122,10 @@ class KMEngine {
   uint16_t* lower_blocks_ = nullptr;
   Pinned<double> host_out_;
   Event ev0_, ev1_;
+  // score() only, allocated by its first call
+  double *dist2_ = nullptr, *cost_part_ = nullptr;   // [R] | [partials + 1]: the partials, then the cost
+  size_t cost_parts_ = 0;
+  Pinned<void> score_host_;            // [R] rows | [R] dist2 | cost | [k] sizes | [R] labels
 };
 
 void bind_kmeans(pybind11::module_& m);

@@ -46,6 +46,17 @@ void launch_km_update(double* centers, double* weights, const double* sums, cons
                       float* cnorm, int dp, hipStream_t s);
 void launch_km_centers32(const double* centers, int k, int d, int dp, float* c32, float* cnorm,
                          hipStream_t s);
+// Scoring: dist2[p] = sum_j (double(X[p][j]) f64[j] - centers[labels[p]][j])^2
+// for the n > 0 rows (n == counters[0]), cost[0] = their sum in an order fixed
+// by (n, dp), sizes[k] = rows per cluster.  partials: scratch of
+// ceil(n / km_cost_shape(dp).rows_per_wg) doubles.
+struct KmCostShape {
+  int lanes_per_row, rows_per_wave, rows_per_wg;
+};
+KmCostShape km_cost_shape(int dp);
+void launch_km_cost(const float* X, const double* f64, const int32_t* labels, const double* centers,
+                    const int64_t* counters, int64_t n, int k, int d, int dp, double* dist2,
+                    double* partials, double* cost, int64_t* sizes, hipStream_t s);
 
 // from featurize.hip
 void launch_filter_only(const DevRawBatch& b, const DevPrepared& p, const FeaturizeParams& fp,

@@ -10,12 +10,23 @@ A LogisticRegressionModel directory (the logistic driver's ``--checkpoint``) is
 scored as such: the output is chosen by the model class found in ``--model`` --
 the class (1.0 / 0.0) under the model's saved threshold, or the probability if
 the model was saved with its threshold cleared.
+A KMeansModel directory (the k-means driver's ``--checkpoint``) is the third
+model class: every batch's retweets (the training filter) are assigned to the
+saved centres -- k and ``text_dims = d - 2`` come from the centres, ``-f`` does
+not apply -- after the per-batch StandardScaler of the training driver
+(``KMeans.scala:103``) or the frozen one of ``--scalerStd``; the outputs are
+the labels, each row's squared distance to its centre and the batch's cost
+(their sum, ``KMeansModel.computeCost``).
 
 ``--model DIR``       the model directory; its weight count must be
                       ``numTextFeatures + 4`` (``-f`` / ``--hash`` as trained)
 ``--predictOut DIR``  per batch ``pred_<seq>.npy`` (float64), ``rows_<seq>.npy``
                       (int64 raw row ids) and one line of ``predictions.jsonl``
                       (batch time, count, mean / min / max prediction, ms)
+                      k-means: ``pred`` is int32 labels, plus ``dist2_<seq>.npy``
+                      (float64); the line holds count, cost, mean_cost,
+                      clusters_used, ms
+``--scalerStd FILE``  k-means: ``.npy`` of d column stds, the frozen scaler
 ``--numBatches N``    stop after N batches
 
 With more than one rank (``rocm[N>1]``, one process per GPU) every rank
@@ -43,7 +54,7 @@ from ..utils.logging import setup_logging
 from ._common import exit_on_sigterm
 from .linear_regression import build_engine
 
-__all__ = ["main", "ScoreJob"]
+__all__ = ["main", "ScoreJob", "KMeansScoreJob", "build_kmeans_scorer"]
 
 log = logging.getLogger("com.giorgioinf.twtml.spark.Score")
 APP_NAME = "twitter-stream-ml-score"
@@ -92,6 +103,56 @@ class ScoreJob:
             self._jsonl = None
 
 
+class KMeansScoreJob(ScoreJob):
+    """Per-batch logic of the scoring driver with a k-means model: the
+    retweets' clusters, squared distances and the batch's cost."""
+
+    def __init__(self, engine, text_dims: int, scaler="batch", out_dir: str = "", rank: int = 0, world: int = 1):
+        super().__init__(engine, out_dir, rank, world)
+        self.scaler = scaler
+        # the CPU engine takes the feature width per call (it holds no config)
+        self._kw = {} if hasattr(engine, "cfg") else {"text_dims": int(text_dims)}
+
+    def on_batch(self, rdd, time_ms: int) -> None:
+        raw = rdd.raw
+        t0 = time.perf_counter()
+        res = self.engine.predict_batch(raw, apply_filter=True, scaler=self.scaler, **self._kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        n = int(res["n_scored"])
+        seq = self.batches
+        self.batches += 1
+        self.scored += n
+        cost = float(res["cost"])
+        rec = {"seq": seq, "batch_time_ms": int(time_ms), "count": n, "cost": cost,
+               "mean_cost": cost / n if n else None,
+               "clusters_used": int(np.count_nonzero(res["sizes"])),
+               "ms": round(ms, 3), "score_ms": round(float(res.get("score_ms", 0.0)), 3)}
+        log.debug("batch %d: %d tweets clustered in %.3f ms, cost %g", seq, n, ms, cost)
+        if self.out_dir:
+            for name, arr, dt in (("pred", res["pred"], np.int32), ("dist2", res["dist2"], np.float64),
+                                  ("rows", res["rows"], np.int64)):
+                np.save(os.path.join(self.out_dir, f"{name}_{seq}{self.suffix}.npy"), np.asarray(arr, dt))
+            self._jsonl.write(json.dumps(rec) + "\n")
+            self._jsonl.flush()
+
+
+def build_kmeans_scorer(conf, centers: np.ndarray, weights: np.ndarray, device: Optional[int]):
+    """The engine that scores with a loaded k-means model: a DeviceKMeans on
+    ``device`` (no communicator: every rank scores its own shard) or, with
+    ``device`` None, the fp64 CpuKMeans."""
+    k, dim = centers.shape
+    if device is not None:
+        from ..ops.kmeans_engine import DeviceKMeans, KMDeviceConfig
+        rows = max(65536, conf.batchSize)
+        engine = DeviceKMeans(KMDeviceConfig(k=k, text_dims=dim - 2, max_rows=rows, max_units=rows * 290,
+                                             seed=conf.seed), device=device)
+    else:
+        from ..models.kmeans import CpuKMeans
+        engine = CpuKMeans(k, dim, seed=conf.seed)
+    engine.set_state(centers, weights)
+    return engine
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     setup_logging()
     exit_on_sigterm()
@@ -102,10 +163,16 @@ def main(argv: Optional[List[str]] = None) -> int:
         print("twtml-score: --model <MLlib model directory> is required", file=sys.stderr)
         return 2
     output = None
+    km = None
     try:
-        from ..checkpoint.saveable import LOGISTIC_CLASS, model_class
-        logistic = model_class(conf.model) == LOGISTIC_CLASS
-        if logistic:
+        from ..checkpoint.saveable import KMEANS_CLASS, LOGISTIC_CLASS, model_class
+        cls = model_class(conf.model)
+        logistic = cls == LOGISTIC_CLASS
+        if cls == KMEANS_CLASS:
+            from ..models.kmeans import StreamingKMeansModel
+            km = StreamingKMeansModel.load(conf.model)
+            w = km.clusterCenters
+        elif logistic:
             from ..models.logistic_regression import LogisticRegressionModel
             m = LogisticRegressionModel.load(conf.model)
             w = m.weights
@@ -117,8 +184,24 @@ def main(argv: Optional[List[str]] = None) -> int:
     except Exception as e:   # noqa: BLE001 -- any unreadable model is the same usage error
         print(f"twtml-score: cannot load the model at {conf.model}: {e}", file=sys.stderr)
         return 2
+    scaler = "batch"
+    if km is not None:
+        text_dims = (w.shape[1] if w.ndim == 2 else 0) - 2
+        if w.shape[0] < 1 or text_dims < 0 or text_dims > 4000:
+            print(f"twtml-score: the k-means model at {conf.model} has centres of shape {w.shape}; the engine takes "
+                  f"k >= 1 centres of 2 + text_dims columns, text_dims in [0, 4000]", file=sys.stderr)
+            return 2
+        if conf.scalerStd:
+            try:
+                scaler = np.asarray(np.load(conf.scalerStd), np.float64)
+                if scaler.shape != (w.shape[1],):
+                    raise ValueError(f"{scaler.shape[0] if scaler.ndim == 1 else scaler.shape} stds for "
+                                     f"{w.shape[1]} columns")
+            except Exception as e:   # noqa: BLE001 -- unreadable or misshapen: the same usage error
+                print(f"twtml-score: cannot use --scalerStd {conf.scalerStd}: {e}", file=sys.stderr)
+                return 2
     want = conf.effectiveNumTextFeatures + 4
-    if w.shape[0] != want:
+    if km is None and w.shape[0] != want:
         print(f"twtml-score: the model at {conf.model} has {w.shape[0]} weights, but numTextFeatures + 4 = {want} "
               f"(give the -f / --numTextFeatures the model was trained with)", file=sys.stderr)
         return 2
@@ -129,9 +212,13 @@ def main(argv: Optional[List[str]] = None) -> int:
     MllibHelper.reset(conf)
     # every rank scores alone: an engine without a communicator, on its GPU
     dev = (spec.devices[rank] if spec.devices else rank) if spec.is_gpu else None
-    engine = build_engine(conf, 0, 1, device=dev, loss="logistic" if logistic else "squared")
-    engine.set_weights(w)
-    log.info("scoring with %d weights from %s", w.shape[0], conf.model)
+    if km is not None:
+        engine = build_kmeans_scorer(conf, km.clusterCenters, km.clusterWeights, dev)
+        log.info("scoring with %d centres of %d columns from %s", w.shape[0], w.shape[1], conf.model)
+    else:
+        engine = build_engine(conf, 0, 1, device=dev, loss="logistic" if logistic else "squared")
+        engine.set_weights(w)
+        log.info("scoring with %d weights from %s", w.shape[0], conf.model)
 
     cap = getattr(engine, "cfg", None)
     ssc = StreamingContext(conf.seconds, batch_size=conf.batchSize, num_batches=conf.numBatches,
@@ -141,7 +228,10 @@ def main(argv: Optional[List[str]] = None) -> int:
                            clock=streaming_clock())
     stream = ssc.twitterStream(make_source(conf.source, rate=conf.sourceRate, seed=conf.seed,
                                            shard=rank, num_shards=world, start=0, batch_size=conf.batchSize)).cache()
-    job = ScoreJob(engine, conf.predictOut, rank, world, output)
+    if km is not None:
+        job = KMeansScoreJob(engine, text_dims, scaler, conf.predictOut, rank, world)
+    else:
+        job = ScoreJob(engine, conf.predictOut, rank, world, output)
     stream.foreachRDD(job.on_batch)
     ssc.start()
     try:

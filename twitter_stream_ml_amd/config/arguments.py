@@ -18,7 +18,8 @@ Extensions for the MI355X engine are long flags only (the reference's 16
 short letters keep their meaning): ``--source``, ``--batchSize``,
 ``--numBatches``, ``--hash``, ``--checkpoint``, ``--checkpointInterval``,
 ``--resume``, ``--sourceRate``, ``--plotPoints``, ``--legacyNumTextFeatures``,
-``--batchTimeout``, ``--checkReplicas``.
+``--batchTimeout``, ``--checkReplicas``, ``--model``, ``--predictOut``,
+``--scalerStd``.
 The master accepts, besides Spark's ``local``, ``local[N]``, ``local[*]``
 (CPU plumbing engine, fp64), the device masters ``rocm``, ``rocm[N]``,
 ``rocm[*]`` and ``rocm:0,1,...`` (HIP engine, one process per GPU).
@@ -140,6 +141,7 @@ _EXT_FLAGS = {
     # apps/score.py (the training drivers ignore them)
     "--model": ("model", str),
     "--predictOut": ("predictOut", str),
+    "--scalerStd": ("scalerStd", str),
     # apps/logistic_regression.py (and apps/score.py with a logistic model)
     "--labelThreshold": ("labelThreshold", int),
     "--threshold": ("threshold", float),
@@ -202,6 +204,7 @@ class ConfArguments:
         self.checkReplicas = 0
         self.model = ""        # apps/score.py: MLlib model directory to score with
         self.predictOut = ""   # apps/score.py: directory of the per-batch prediction files
+        self.scalerStd = ""    # apps/score.py, k-means models: .npy of d column stds (frozen scaler)
         # apps/logistic_regression.py: label = retweetCount >= labelThreshold (-1: middle of the
         # filter range), class 1 when the probability exceeds threshold
         self.labelThreshold = c.getInt("labelThreshold") if c.hasPath("labelThreshold") else -1
@@ -246,6 +249,8 @@ Usage: twtml-spark [options]
   --legacyNumTextFeatures                         reproduce the reference bug: ignore -f
   --model <dir>  --predictOut <dir>               scoring driver (apps.score / twtml-score): the MLlib
                                                   model directory to load, where predictions go
+  --scalerStd <file.npy>                          scoring driver, k-means models: the d column stds of a
+                                                  frozen scaler (default: a StandardScaler fitted per batch)
   --labelThreshold <n>  --threshold <p>           logistic driver (apps.logistic_regression / twtml-logistic):
                                                   class 1 is retweetCount >= n (default: middle of -B..-E);
                                                   predicted class 1 when the probability exceeds p (0.5)

@@ -19,6 +19,7 @@
 from __future__ import annotations
 
 import math
+import time
 from typing import Callable, Dict, Optional
 
 import numpy as np
@@ -29,15 +30,16 @@ from ..records.batch import FOLLOWERS, RETWEET_COUNT, RawBatch
 from .vectors import DenseVector, Vector
 
 __all__ = ["StreamingKMeans", "StreamingKMeansModel", "StandardScaler", "StandardScalerModel",
-           "kmeans_features", "CpuKMeans"]
+           "kmeans_features", "CpuKMeans", "scaler_mode", "empty_score"]
 
 BATCHES = "batches"
 POINTS = "points"
 
 
-def kmeans_features(raw: RawBatch, text_dims: int = 0, hash: str = "java"):
-    """Dense (n_retweets, 2 + text_dims) fp64 features and the kept row ids."""
-    rows = np.nonzero(raw.is_retweet != 0)[0].astype(np.int64)
+def kmeans_features(raw: RawBatch, text_dims: int = 0, hash: str = "java", apply_filter: bool = True):
+    """Dense (n_retweets, 2 + text_dims) fp64 features and the kept row ids
+    (``apply_filter`` off: every row, for scoring)."""
+    rows = (np.nonzero(raw.is_retweet != 0)[0] if apply_filter else np.arange(raw.n)).astype(np.int64)
     n = rows.shape[0]
     X = np.zeros((n, 2 + text_dims))
     X[:, 0] = raw.scalars[RETWEET_COUNT, rows]
@@ -49,6 +51,31 @@ def kmeans_features(raw: RawBatch, text_dims: int = 0, hash: str = "java"):
         r = np.repeat(np.arange(n), np.diff(indptr))
         np.add.at(X, (r, 2 + idx), 1.0)
     return X, rows
+
+
+# predict_batch's scaler modes, as KMEngine::score numbers them
+SCALER_BATCH, SCALER_GIVEN, SCALER_NONE = 0, 1, 2
+
+
+def scaler_mode(scaler, dim: int, scale: bool = True):
+    """``predict_batch``'s ``scaler`` argument -> (mode, std or None): "batch"
+    (per-batch fit; "none" for an engine that does not scale), "none", or an
+    array of ``dim`` stds (frozen)."""
+    if isinstance(scaler, str):
+        if scaler not in ("batch", "none"):
+            raise ValueError(f"unknown scaler {scaler!r} (batch, none or an array of {dim} stds)")
+        return (SCALER_BATCH if scaler == "batch" and scale else SCALER_NONE), None
+    std = np.ascontiguousarray(scaler, dtype=np.float64)
+    if std.shape != (dim,):
+        raise ValueError(f"the scaler needs {dim} stds, got shape {std.shape}")
+    return SCALER_GIVEN, std
+
+
+def empty_score(n_raw: int, k: int, std=None) -> Dict[str, object]:
+    """``predict_batch`` of a batch with nothing to score."""
+    return {"n_raw": int(n_raw), "n_scored": 0, "rows": np.zeros(0, np.int64), "pred": np.zeros(0, np.int32),
+            "dist2": np.zeros(0, np.float64), "cost": 0.0, "sizes": np.zeros(int(k), np.int64),
+            "std": None if std is None else std.copy(), "score_ms": 0.0, "wall_ms": 0.0}
 
 
 class StandardScalerModel:
@@ -214,3 +241,28 @@ class CpuKMeans:
         # KMeans.scala:113 predicts with the *updated* model
         pred = find_closest(self.state.centers, Xs) if Xs.shape[0] else np.zeros(0, np.int64)
         return {"n": int(n), "labels": labels, "pred": pred, "std": std, "scaled": Xs}
+
+    def predict_batch(self, raw: RawBatch, text_dims: int, apply_filter: bool = True,
+                      scaler="batch") -> Dict[str, object]:
+        """The contract of ``DeviceKMeans.predict_batch`` in fp64 (its oracle):
+        closest centre, squared distance to it in the scaled space, their sum
+        (``KMeansModel.computeCost``) and the rows per cluster of a raw batch
+        under the current model, which is left as it is.  The per-batch scaler
+        is fitted on the scored rows of this process alone."""
+        t0 = time.perf_counter()
+        k, dim = self.state.centers.shape
+        if dim != 2 + text_dims:
+            raise ValueError(f"the model has {dim} columns, text_dims + 2 = {2 + text_dims}")
+        mode, std = scaler_mode(scaler, dim, self.scale)
+        X, rows = kmeans_features(raw, text_dims, apply_filter=apply_filter)
+        if X.shape[0] == 0:
+            return empty_score(raw.n, k, std)
+        if mode == SCALER_BATCH:
+            std = standard_scaler_fit(X)
+        Xs = X if std is None else standard_scaler_transform(X, std)
+        pred = find_closest(self.state.centers, Xs)
+        dist2 = ((Xs - self.state.centers[pred]) ** 2).sum(axis=1)
+        ms = (time.perf_counter() - t0) * 1e3
+        return {"n_raw": int(raw.n), "n_scored": int(X.shape[0]), "rows": rows, "pred": pred.astype(np.int32),
+                "dist2": dist2, "cost": float(dist2.sum()), "sizes": np.bincount(pred, minlength=k).astype(np.int64),
+                "std": std, "score_ms": ms, "wall_ms": ms}

@@ -21,10 +21,12 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
+import time
 import weakref
 
 import numpy as np
 
+from ..models.kmeans import empty_score, scaler_mode
 from ..oracle.mllib import KMeansState, decay_factor_from_half_life
 from ..records.batch import RawBatch
 from ._native import hip
@@ -152,6 +154,37 @@ class DeviceKMeans:
     def update_raw(self, raw: RawBatch, want_pred: bool = True) -> Dict[str, object]:
         """One micro-batch: uses its prefetched slot, else stages + H2D now."""
         return self.process(self._pipe.take(raw), want_pred)
+
+    # ---- inference (KMEngine::score, k_km_cost) ---------------------------
+    def predict_batch(self, raw: RawBatch, apply_filter: bool = True, scaler="batch") -> Dict[str, object]:
+        """Assign one raw micro-batch to the current clusters, without training
+        on it (``StreamingKMeans.predictOn`` + ``KMeansModel.computeCost``):
+        ``rows`` (int64 raw row ids, ascending), ``pred`` (int32 closest
+        centre), ``dist2`` (fp64 squared distance to it in the scaled space),
+        ``cost`` (their sum, summed on the device in a fixed order), ``sizes``
+        (int64[k] rows per cluster), ``std`` (the column stds used, None
+        without a scaler), ``n_raw``, ``n_scored``, ``score_ms`` (device time of
+        the kernels), ``wall_ms``.  ``apply_filter``: only the retweets, as
+        training; off: every row.  ``scaler``: ``"batch"`` (a StandardScaler
+        fitted on the scored rows, what the training driver does per batch;
+        ``"none"`` when ``cfg.scale`` is off), ``"none"``, or an array of d stds
+        (a frozen scaler: a row's result then depends on the row and the model
+        alone).  The batch is staged into a raw slot no prefetched batch holds;
+        the model and the prefetched batches are left as they are.  Call it
+        from the thread that calls ``update_raw``."""
+        mode, std = scaler_mode(scaler, self.dim, bool(self.cfg.scale))
+        if raw.n == 0:                # nothing is staged or launched
+            return empty_score(0, self.cfg.k, std)
+        t0 = time.perf_counter()
+        slot = self._pipe.free_slot()
+        try:
+            self.submit(self._stage(slot, raw), slot)
+            r = self._eng.score(int(slot), bool(apply_filter), mode, std)
+        finally:
+            self._pipe.score_done(slot)
+        r["std"] = std.copy() if std is not None else (np.asarray(r["std"]) if len(r["std"]) else None)
+        r["wall_ms"] = (time.perf_counter() - t0) * 1e3
+        return r
 
     @property
     def h2d_bytes(self) -> int:
