@@ -373,6 +373,34 @@ PYBIND11_MODULE(_twtml_hip, m) {
            "inference only: fp64 predictions of the batch in `slot` (submitted with train=False) under the "
            "current weights; rows = raw row ids (ascending), pred in that order; link 0 margin, "
            "1 probability, 2 class (margin > logit(threshold))")
+      .def("evaluate",
+           [](LREngine& e, int slot, int64_t now_ms, bool apply_filter) {
+             EvalResult r;
+             {
+               py::gil_scoped_release nogil;
+               r = e.evaluate(slot, now_ms, apply_filter);
+             }
+             // copies owned by the caller (the engine's pinned buffer is reused); zeros for an empty batch
+             py::array_t<int64_t> iw(kEvalIntWords);
+             py::array_t<double> dw(kEvalF64Words);
+             std::memset(iw.mutable_data(), 0, sizeof(int64_t) * kEvalIntWords);
+             std::memset(dw.mutable_data(), 0, sizeof(double) * kEvalF64Words);
+             if (r.iw) std::memcpy(iw.mutable_data(), r.iw, sizeof(int64_t) * kEvalIntWords);
+             if (r.dw) std::memcpy(dw.mutable_data(), r.dw, sizeof(double) * kEvalF64Words);
+             py::dict d;
+             d["n_raw"] = r.n_raw;
+             d["n_scored"] = r.n_scored;
+             d["binary"] = r.binary;
+             d["iw"] = iw;
+             d["dw"] = dw;
+             d["eval_ms"] = r.eval_ms;
+             d["wall_ms"] = r.wall_ms;
+             return d;
+           },
+           py::arg("slot"), py::arg("now_ms"), py::arg("apply_filter") = false,
+           "held-out evaluation of the batch in `slot` (submitted with train=False) under the current weights: "
+           "iw = the int64 accumulator words (n, n_nan, tn, fp, fn, tp, -, scored rows, hist[2][4097]), "
+           "dw = the fp64 sums (kernels.h launch_eval)")
       .def("process",
            [](LREngine& e, int slot, int64_t now_ms, bool want_pred, int64_t plot_points) {
              BatchResult r;

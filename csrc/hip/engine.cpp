@@ -596,6 +596,67 @@ ScoreResult LREngine::score(int slot, int64_t now_ms, bool apply_filter, int lin
 }
 
 // ---------------------------------------------------------------------------
+// Held-out evaluation (eval.hip): score()'s pass, then the metric accumulators.
+// ---------------------------------------------------------------------------
+void LREngine::ensure_eval() {
+  ensure_score();
+  if (eval_out_) return;
+  static_assert(sizeof(int64_t) == sizeof(double), "one buffer holds both kinds of accumulator words");
+  eval_part_ = score_arena_.alloc<double>(size_t(kEvalMaxGrid) * kEvalF64Words);
+  eval_host_.alloc(sizeof(int64_t) * (kEvalIntWords + kEvalF64Words), hipHostMallocDefault);
+  eval_ev_[0] = Event(hipEventDefault);
+  eval_ev_[1] = Event(hipEventDefault);
+  eval_out_ = score_arena_.alloc<int64_t>(kEvalIntWords + kEvalF64Words);
+}
+
+EvalResult LREngine::evaluate(int slot, int64_t now_ms, bool apply_filter) {
+  TraceRange tr("twtml.lr.eval");
+  TWTML_HIP_CHECK(hipSetDevice(device_));
+  const auto t_in = std::chrono::steady_clock::now();
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (training_owns_locked(slot))
+      throw std::logic_error("evaluate(): the slot holds a batch queued or prepared for training");
+  }
+  EvalResult res;
+  res.binary = cfg_.loss == kLossLogistic;
+  res.n_raw = raw_.rows(slot);
+  if (res.n_raw == 0) return res;
+  ensure_eval();
+  hipStream_t s = compute_;
+  const DevRawBatch b = raw_.acquire(slot, s);
+  const int64_t n = b.n;
+  FeaturizeParams fp{cfg_.num_text_features, cfg_.hash_kind, apply_filter ? cfg_.require_retweet : 0,
+                     apply_filter ? cfg_.range_filter : 0, cfg_.begin, cfg_.end, now_ms};
+  double* pred = reinterpret_cast<double*>(score_out_ + 8);
+  int64_t* rows = apply_filter ? score_out_ + 8 + n : nullptr;
+  double* out_d = reinterpret_cast<double*>(eval_out_ + kEvalIntWords);
+  TWTML_HIP_CHECK(hipEventRecord(eval_ev_[0], s));
+  launch_score_init(score_dp_, s);
+  launch_filter_sort(b, score_dp_, fp, s);
+  launch_chunk_layout(b, score_dp_, s);
+  launch_score(b, score_dp_, fp, lower_page_, lower_blocks_, sgd_.w64, pred, rows, s, kLinkMargin, 0.0);
+  launch_eval(b, pred, rows, score_dp_.counters, res.binary ? cfg_.label_threshold : -1, logit_threshold(), eval_out_,
+              out_d, eval_part_, s);
+  TWTML_HIP_CHECK(hipEventRecord(eval_ev_[1], s));
+  raw_.release_slot(slot, s);   // the raw slot may be overwritten now
+  TWTML_HIP_CHECK(hipMemcpyAsync(eval_host_.get(), eval_out_, sizeof(int64_t) * (kEvalIntWords + kEvalF64Words),
+                                 hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipStreamSynchronize(s));
+  const int64_t* h = eval_host_.get();
+  res.n_scored = h[kEvalScored];
+  if (res.n_scored < 0 || res.n_scored > n || (!apply_filter && res.n_scored != n))
+    throw std::runtime_error("evaluate(): kept-row count out of range");
+  if (h[kEvalN] + h[kEvalNan] != res.n_scored)
+    throw std::runtime_error("evaluate(): the accumulator does not hold every scored row");
+  res.iw = h;
+  res.dw = reinterpret_cast<const double*>(h + kEvalIntWords);
+  TWTML_HIP_CHECK(hipEventElapsedTime(&res.eval_ms, eval_ev_[0], eval_ev_[1]));
+  res.wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+  return res;
+}
+
+// ---------------------------------------------------------------------------
 // prepare: filter .. layout of one raw slot into a PrepBuf, on stream `s`
 // (the prep stream; host syncs for the batch's counts stay on this thread).
 // One GPU: prepare_local + prepare_global.  DP: prepare_local (ends with the

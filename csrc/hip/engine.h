@@ -174,6 +174,18 @@ struct ScoreResult {
   float wall_ms = 0.f;             // score() on the host, end to end
 };
 
+// evaluate(): the metric accumulators of one raw batch (kernels.h
+// launch_eval).  iw / dw point into the engine's pinned buffer and stay valid
+// until the next evaluate() call.
+struct EvalResult {
+  int64_t n_raw = 0, n_scored = 0;
+  bool binary = false;             // the logistic accumulator (else the regression one)
+  const int64_t* iw = nullptr;     // [kEvalIntWords]; null when n_raw == 0
+  const double* dw = nullptr;      // [kEvalF64Words]
+  float eval_ms = 0.f;             // device time, filter .. k_eval_final (events)
+  float wall_ms = 0.f;             // evaluate() on the host, end to end
+};
+
 // One prepared micro-batch: filtered, featurized, compacted and laid out for
 // the GD kernels.  Two of them, so batch t+1 is prepared on the prep stream
 // (by the engine's prep thread) while batch t trains on the compute stream.
@@ -254,6 +266,15 @@ class LREngine {
   // score() and process() must be called from the same thread.
   // link: kLinkMargin / kLinkProbability / kLinkClass (kernels.h), applied on the device
   ScoreResult score(int slot, int64_t now_ms, bool apply_filter, int link = 0);
+  // Held-out evaluation: score()'s pass with kLinkMargin, then the scored
+  // rows' (margin, retweetCount) pairs reduced on the device (eval.hip) into
+  // the binary accumulator (logistic loss: label = retweetCount >=
+  // label_threshold, class 1 when margin > logit_threshold()) or the
+  // regression one.  Only the accumulator words cross to the host (~66 KB, one
+  // copy); neither the predictions nor the row ids do.  Same preconditions
+  // and guarantees as score(): nothing of the model but the weights is read,
+  // no collective is issued, same thread as process().
+  EvalResult evaluate(int slot, int64_t now_ms, bool apply_filter);
   // Forget a submitted batch that will not be processed (one GPU only): the
   // slot may be submitted again afterwards (ops/ingest.py SlotPipeline).
   void discard(int slot);
@@ -318,6 +339,7 @@ class LREngine {
  private:
   void alloc_prepared(PrepBuf& b);
   void ensure_score();
+  void ensure_eval();
   bool training_owns_locked(int slot) const;
   void ensure_compact(int64_t ns);
   void ensure_part(int64_t n);
@@ -407,6 +429,13 @@ class LREngine {
   int64_t* score_out_ = nullptr;      // device [8 + 2 max_rows]
   Pinned<int64_t> score_host_;        // pinned  [8 + 2 max_rows]
   Event score_ev_[2];
+  // evaluate(): the accumulator words [kEvalIntWords int64 | kEvalF64Words
+  // fp64] and the workgroup partials, from score_arena_, and the words'
+  // pinned host copy; allocated by the first evaluate()
+  int64_t* eval_out_ = nullptr;
+  double* eval_part_ = nullptr;       // device [kEvalMaxGrid][kEvalF64Words]
+  Pinned<int64_t> eval_host_;
+  Event eval_ev_[2];
   // weight snapshot (snapshot.hip); allocated on the first snapshot_begin
   std::mutex snap_mu_;
   bool snap_pending_ = false;

@@ -256,6 +256,34 @@ void launch_score(const DevRawBatch& b, const DevPrepared& p, const FeaturizePar
                   const uint16_t* lower_blocks, const double* w64, double* pred, int64_t* rows, hipStream_t s,
                   int link = kLinkMargin, double logit_thr = 0.0);
 
+// ---------------------------------------------------------------------------
+// Held-out evaluation (eval.hip): the (margin, label) pairs of a scored batch
+// reduced into the accumulators of models/metrics.py.  Follows launch_score
+// (kLinkMargin) on the same stream: pred / rows are its outputs (rows null
+// when unfiltered), counters[0] its scored-row count on the device; the label
+// is scalar column 0 (retweetCount) of raw row rows[k].
+//   out_i [kEvalIntWords] int64: n, n_nan, tn, fp, fn, tp, -, counters[0]
+//         (the scored rows), then hist[2][kEvalBins] (label, margin bin);
+//         regression: n, n_nan and the scored rows only
+//   out_d [kEvalF64Words] fp64: logloss_sum, or the sums of y, y^2, p, p^2,
+//         (y - p)^2, |y - p|
+//   partials [kEvalMaxGrid][kEvalF64Words] scratch
+// label_threshold >= 0: binary (label = retweetCount >= label_threshold, class
+// 1 predicted when margin > logit_thr); < 0: regression.  NaN margins count in
+// n_nan and nowhere else.  out_i is zeroed on `s` first; every word of out_d
+// is written.
+constexpr int kEvalBins = 4097;
+constexpr int kEvalIntHead = 8;
+constexpr int kEvalN = 0, kEvalNan = 1, kEvalConf = 2, kEvalScored = 7;
+constexpr int kEvalIntWords = kEvalIntHead + 2 * kEvalBins;
+constexpr int kEvalF64Words = 8;
+constexpr int kEvalMaxGrid = 256;
+// workgroups of a batch of n_raw rows (the fp64 sum order is a function of it)
+int eval_grid(int64_t n_raw);
+void launch_eval(const DevRawBatch& b, const double* pred, const int64_t* rows, const int64_t* counters,
+                 int64_t label_threshold, double logit_thr, int64_t* out_i, double* out_d, double* partials,
+                 hipStream_t s);
+
 // Exclusive int64 scan (in place safe); tsum: ceil(n / 2048) + 2 scratch.
 void launch_scan_excl(const int64_t* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum, hipStream_t s,
                       int64_t* out2 = nullptr);

@@ -113,7 +113,11 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-f
 # Per-source extras.  kmeans.hip: MFMA accumulators in VGPRs (the k-means
 # assignment reads every accumulator on the VALU after each tile; AGPR
 # accumulators cost a v_accvgpr_read per value -- 16 of ~128 VALU per tile).
-HIP_FILE_FLAGS = {"kmeans.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+# eval.hip: no contraction (-ffp-contract=fast disregards the source's pragma):
+# every per-row term of the evaluation sums is a sequence of single IEEE
+# operations that the host reproduces bit for bit (models/metrics.py).
+HIP_FILE_FLAGS = {"kmeans.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+                  "eval.hip": ["-ffp-contract=off"]}
 
 
 def build_hip(force: bool = False, verbose: bool = False) -> str:

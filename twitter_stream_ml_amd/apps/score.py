@@ -26,12 +26,28 @@ the labels, each row's squared distance to its centre and the batch's cost
                       k-means: ``pred`` is int32 labels, plus ``dist2_<seq>.npy``
                       (float64); the line holds count, cost, mean_cost,
                       clusters_used, ms
+``--evalOut DIR``     held-out evaluation of a linear or logistic model against the
+                      stream's own ``retweetCount`` (``engine.evaluate_batch``; on
+                      ``rocm[N]`` the reduction of ``csrc/hip/eval.hip`` behind the
+                      scoring kernels, ~66 KB per batch back to the host): per batch
+                      one line of ``metrics.jsonl`` -- seq, batch time, count, the
+                      batch's metrics (``models/metrics.py``: MLlib's
+                      ``BinaryClassificationMetrics`` with ``auc_tie_bound`` next to
+                      the AUC, or ``RegressionMetrics``), the accumulator itself and
+                      ms -- and at the end ``summary.json``, the metrics of the
+                      accumulator merged over all batches.  Logistic models: class 1
+                      is ``retweetCount >= --labelThreshold`` (default: the middle of
+                      ``-B..-E``, as in the training driver).  May be combined with
+                      ``--predictOut`` (both passes run).  A k-means model with
+                      ``--evalOut`` is a usage error (exit code 2): ``cost`` is its
+                      metric already.  Nothing is posted to twtml-web.
 ``--scalerStd FILE``  k-means: ``.npy`` of d column stds, the frozen scaler
 ``--numBatches N``    stop after N batches
 
 With more than one rank (``rocm[N>1]``, one process per GPU) every rank
 scores its own shard of the stream and writes its own files, suffixed
-``_r<rank>``; scoring needs no collective.
+``_r<rank>``; scoring needs no collective.  The ranks' ``metrics_r<rank>.jsonl``
+accumulators combine exactly with ``EvalAccumulator.from_dict`` + ``merge``.
 """
 from __future__ import annotations
 
@@ -54,7 +70,7 @@ from ..utils.logging import setup_logging
 from ._common import exit_on_sigterm
 from .linear_regression import build_engine
 
-__all__ = ["main", "ScoreJob", "KMeansScoreJob", "build_kmeans_scorer"]
+__all__ = ["main", "ScoreJob", "KMeansScoreJob", "EvalJob", "build_kmeans_scorer"]
 
 log = logging.getLogger("com.giorgioinf.twtml.spark.Score")
 APP_NAME = "twitter-stream-ml-score"
@@ -136,6 +152,50 @@ class KMeansScoreJob(ScoreJob):
             self._jsonl.flush()
 
 
+class EvalJob:
+    """Per-batch logic of ``--evalOut``: the batch's accumulator and metrics
+    as one line of ``metrics.jsonl``, the merged accumulator's metrics in
+    ``summary.json`` at the end."""
+
+    def __init__(self, engine, out_dir: str, rank: int = 0, world: int = 1):
+        self.engine = engine
+        self.out_dir = out_dir
+        self.suffix = f"_r{rank}" if world > 1 else ""
+        self.batches = 0
+        self.total = None
+        os.makedirs(out_dir, exist_ok=True)
+        self._jsonl = open(os.path.join(out_dir, f"metrics{self.suffix}.jsonl"), "a", encoding="utf-8")
+
+    def on_batch(self, rdd, time_ms: int) -> None:
+        from ..models.metrics import EvalAccumulator
+        t0 = time.perf_counter()
+        res = self.engine.evaluate_batch(rdd.raw, apply_filter=False)
+        ms = (time.perf_counter() - t0) * 1e3
+        acc = EvalAccumulator.like(res).add(res)
+        if self.total is None:
+            self.total = EvalAccumulator.like(res)
+        self.total.merge(acc)
+        seq = self.batches
+        self.batches += 1
+        rec = {"seq": seq, "batch_time_ms": int(time_ms), "count": int(res["n_scored"]),
+               "metrics": acc.metrics().to_dict(), "accumulator": acc.to_dict(),
+               "ms": round(ms, 3), "eval_ms": round(float(res.get("eval_ms", 0.0)), 3)}
+        self._jsonl.write(json.dumps(rec) + "\n")
+        self._jsonl.flush()
+
+    def close(self) -> None:
+        if self._jsonl is None:
+            return
+        self._jsonl.close()
+        self._jsonl = None
+        summary = {"batches": self.batches}
+        if self.total is not None:
+            summary.update(metrics=self.total.metrics().to_dict(), accumulator=self.total.to_dict())
+        with open(os.path.join(self.out_dir, f"summary{self.suffix}.json"), "w", encoding="utf-8") as f:
+            json.dump(summary, f)
+            f.write("\n")
+
+
 def build_kmeans_scorer(conf, centers: np.ndarray, weights: np.ndarray, device: Optional[int]):
     """The engine that scores with a loaded k-means model: a DeviceKMeans on
     ``device`` (no communicator: every rank scores its own shard) or, with
@@ -183,6 +243,10 @@ def main(argv: Optional[List[str]] = None) -> int:
             w = LinearRegressionModel.load(conf.model).weights
     except Exception as e:   # noqa: BLE001 -- any unreadable model is the same usage error
         print(f"twtml-score: cannot load the model at {conf.model}: {e}", file=sys.stderr)
+        return 2
+    if km is not None and conf.evalOut:
+        print("twtml-score: --evalOut does not apply to a k-means model: its metric is the cost that "
+              "--predictOut already reports", file=sys.stderr)
         return 2
     scaler = "batch"
     if km is not None:
@@ -232,7 +296,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         job = KMeansScoreJob(engine, text_dims, scaler, conf.predictOut, rank, world)
     else:
         job = ScoreJob(engine, conf.predictOut, rank, world, output)
-    stream.foreachRDD(job.on_batch)
+    ev = EvalJob(engine, conf.evalOut, rank, world) if conf.evalOut else None
+    if ev is None or conf.predictOut:
+        stream.foreachRDD(job.on_batch)
+    if ev is not None:
+        stream.foreachRDD(ev.on_batch)
     ssc.start()
     try:
         ssc.awaitTermination()
@@ -241,7 +309,12 @@ def main(argv: Optional[List[str]] = None) -> int:
     finally:
         ssc.stop()
         job.close()
-    log.info("scored %d tweets in %d batches", job.scored, job.batches)
+        if ev is not None:
+            ev.close()
+    if ev is not None:
+        log.info("evaluated %d batches", ev.batches)
+    if ev is None or conf.predictOut:
+        log.info("scored %d tweets in %d batches", job.scored, job.batches)
     return 0
 
 

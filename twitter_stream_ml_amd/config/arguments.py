@@ -19,7 +19,7 @@ short letters keep their meaning): ``--source``, ``--batchSize``,
 ``--numBatches``, ``--hash``, ``--checkpoint``, ``--checkpointInterval``,
 ``--resume``, ``--sourceRate``, ``--plotPoints``, ``--legacyNumTextFeatures``,
 ``--batchTimeout``, ``--checkReplicas``, ``--model``, ``--predictOut``,
-``--scalerStd``.
+``--scalerStd``, ``--evalOut``.
 The master accepts, besides Spark's ``local``, ``local[N]``, ``local[*]``
 (CPU plumbing engine, fp64), the device masters ``rocm``, ``rocm[N]``,
 ``rocm[*]`` and ``rocm:0,1,...`` (HIP engine, one process per GPU).
@@ -142,6 +142,7 @@ _EXT_FLAGS = {
     "--model": ("model", str),
     "--predictOut": ("predictOut", str),
     "--scalerStd": ("scalerStd", str),
+    "--evalOut": ("evalOut", str),
     # apps/logistic_regression.py (and apps/score.py with a logistic model)
     "--labelThreshold": ("labelThreshold", int),
     "--threshold": ("threshold", float),
@@ -205,6 +206,7 @@ class ConfArguments:
         self.model = ""        # apps/score.py: MLlib model directory to score with
         self.predictOut = ""   # apps/score.py: directory of the per-batch prediction files
         self.scalerStd = ""    # apps/score.py, k-means models: .npy of d column stds (frozen scaler)
+        self.evalOut = ""      # apps/score.py: directory of the held-out metrics (metrics.jsonl, summary.json)
         # apps/logistic_regression.py: label = retweetCount >= labelThreshold (-1: middle of the
         # filter range), class 1 when the probability exceeds threshold
         self.labelThreshold = c.getInt("labelThreshold") if c.hasPath("labelThreshold") else -1
@@ -249,6 +251,9 @@ Usage: twtml-spark [options]
   --legacyNumTextFeatures                         reproduce the reference bug: ignore -f
   --model <dir>  --predictOut <dir>               scoring driver (apps.score / twtml-score): the MLlib
                                                   model directory to load, where predictions go
+  --evalOut <dir>                                 scoring driver, linear / logistic models: evaluate the stream
+                                                  against its retweet counts (metrics.jsonl per batch, summary.json;
+                                                  logistic: AUC with its tie bound, class 1 is --labelThreshold)
   --scalerStd <file.npy>                          scoring driver, k-means models: the d column stds of a
                                                   frozen scaler (default: a StandardScaler fitted per batch)
   --labelThreshold <n>  --threshold <p>           logistic driver (apps.logistic_regression / twtml-logistic):

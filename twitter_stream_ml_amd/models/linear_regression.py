@@ -194,6 +194,21 @@ class CpuLinearRegression:
         return {"n_raw": raw.n, "n_scored": int(rows.shape[0]), "rows": rows.astype(np.int64),
                 "pred": pred, "score_ms": (time.perf_counter() - t0) * 1e3}
 
+    def evaluate_batch(self, raw: RawBatch, apply_filter: bool = False,
+                       now_ms: Optional[int] = None) -> Dict[str, object]:
+        """Held-out evaluation (the contract of
+        ``DeviceLinearRegression.evaluate_batch``): the regression accumulator
+        of ``models/metrics.py`` from this engine's own ``predict_batch``
+        margins and the rows' ``retweetCount``."""
+        import time
+        from .metrics import regression_accumulator
+        t0 = time.perf_counter()
+        res = self.predict_batch(raw, apply_filter=apply_filter, now_ms=now_ms)
+        out = regression_accumulator(res["pred"], raw.scalars[RETWEET_COUNT][res["rows"]])
+        ms = (time.perf_counter() - t0) * 1e3
+        out.update(n_raw=raw.n, n_scored=int(res["n_scored"]), eval_ms=ms, wall_ms=ms)
+        return out
+
     def synchronize(self) -> None:
         pass
 

@@ -289,6 +289,23 @@ class CpuLogisticRegression:
         return {"n_raw": raw.n, "n_scored": int(rows.shape[0]), "rows": rows.astype(np.int64),
                 "pred": _link(m, output, c.threshold), "score_ms": (time.perf_counter() - t0) * 1e3}
 
+    def evaluate_batch(self, raw: RawBatch, apply_filter: bool = False,
+                       now_ms: Optional[int] = None) -> Dict[str, object]:
+        """Held-out evaluation (the contract of
+        ``DeviceLogisticRegression.evaluate_batch``): the binary accumulator of
+        ``models/metrics.py`` from this engine's own ``predict_batch`` margins
+        and the labels ``retweetCount >= label_threshold``."""
+        import time
+        from ..records.batch import RETWEET_COUNT
+        from .metrics import binary_accumulator
+        t0 = time.perf_counter()
+        c = self.cfg
+        res = self.predict_batch(raw, apply_filter=apply_filter, now_ms=now_ms, output="margin")
+        out = binary_accumulator(res["pred"], raw.scalars[RETWEET_COUNT][res["rows"]], c.label_threshold, c.threshold)
+        ms = (time.perf_counter() - t0) * 1e3
+        out.update(n_raw=raw.n, n_scored=int(res["n_scored"]), eval_ms=ms, wall_ms=ms)
+        return out
+
     def synchronize(self) -> None:
         pass
 

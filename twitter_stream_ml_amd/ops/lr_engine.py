@@ -441,6 +441,48 @@ class DeviceLinearRegression:
         finally:
             self._pipe.score_done(slot)
 
+    # ---- held-out evaluation (csrc/hip/eval.hip) ---------------------------
+    def evaluate_batch(self, raw: RawBatch, apply_filter: bool = False,
+                       now_ms: Optional[int] = None) -> Dict[str, object]:
+        """Evaluate the current model on one labelled raw micro-batch, without
+        training on it: ``predict_batch``'s margins and the rows'
+        ``retweetCount`` reduced on the device into the accumulator of
+        ``models/metrics.py`` -- ``kind`` ``"binary"`` (logistic loss: ``hist``
+        2 x 4097 int64, ``confusion`` [tn, fp, fn, tp], ``logloss_sum``) or
+        ``"regression"`` (the six ``sum_*``), with ``n``, ``n_nan``, ``n_raw``,
+        ``n_scored``, ``label_threshold``, ``threshold``, ``eval_ms`` (device
+        time, filter through the reduction) and ``wall_ms``.  Only the
+        accumulator (~66 KB) leaves the device.  Feed the result to
+        ``metrics.EvalAccumulator.add`` / ``metrics.metrics_of``.  Staging and
+        guarantees are ``predict_batch``'s."""
+        from ..models import metrics
+        kind = "binary" if self.cfg.loss == "logistic" else "regression"
+        lt = self.cfg.effective_label_threshold() if kind == "binary" else -1
+        self.staging(0)._check(raw)
+        if raw.n == 0:                # nothing is staged or launched
+            out = metrics.empty_result(kind, lt, float(self.cfg.threshold))
+            out.update(n_raw=0, n_scored=0, eval_ms=0.0, wall_ms=0.0)
+            return out
+        slot = self._pipe.free_slot()
+        try:
+            hb = self.staging(slot).load(raw, self.cfg.ingest)
+            self._eng.submit(hb._hb, int(hb.n), int(hb.bytes), int(slot), int(hb.ext_text),
+                             int(hb.batch_time_ms), False)
+            r = self._eng.evaluate(int(slot), int(raw.batch_time_ms if now_ms is None else now_ms),
+                                   bool(apply_filter))
+        finally:
+            self._pipe.score_done(slot)
+        iw, dw = np.asarray(r["iw"]), np.asarray(r["dw"])
+        out = {"kind": kind, "n_raw": int(r["n_raw"]), "n_scored": int(r["n_scored"]), "n": int(iw[0]),
+               "n_nan": int(iw[1]), "label_threshold": lt, "threshold": float(self.cfg.threshold),
+               "eval_ms": float(r["eval_ms"]), "wall_ms": float(r["wall_ms"])}
+        if kind == "binary":
+            out.update(hist=iw[8:8 + 2 * metrics.EVAL_BINS].reshape(2, metrics.EVAL_BINS).copy(),
+                       confusion=[int(v) for v in iw[2:6]], logloss_sum=float(dw[0]))
+        else:
+            out.update({k: float(dw[j]) for j, k in enumerate(metrics.REGRESSION_SUMS)})
+        return out
+
     @property
     def h2d_bytes(self) -> int:
         """Host-to-device bytes submitted so far (every copy of every batch)."""
