@@ -489,6 +489,22 @@ PYBIND11_MODULE(_twtml_hip, m) {
         d["cslot"] = py::array_t<int32_t>(py::ssize_t(cslot.size()), cslot.data());
         return d;
       })
+      .def("debug_far_layout", [](const LREngine& e) {
+        FarLayoutDebug f;
+        e.debug_far_layout(f);
+        py::dict d;
+        d["tiered"] = f.tiered;
+        d["near_end"] = f.near_end;
+        d["far_total"] = f.far_total;
+        d["offsets"] = py::array_t<int64_t>(py::ssize_t(f.offsets.size()), f.offsets.data());
+        d["csc_pos"] = py::array_t<uint32_t>(py::ssize_t(f.csc_pos.size()), f.csc_pos.data());
+        d["csc_slot"] = py::array_t<uint32_t>(py::ssize_t(f.csc_slot.size()), f.csc_slot.data());
+        d["fcount"] = py::array_t<int32_t>(py::ssize_t(f.fcount.size()), f.fcount.data());
+        d["cbase"] = py::array_t<int64_t>(py::ssize_t(f.cbase.size()), f.cbase.data());
+        d["flist"] = py::array_t<uint32_t>(py::ssize_t(f.flist.size()), f.flist.data());
+        d["frank"] = py::array_t<uint32_t>(py::ssize_t(f.frank.size()), f.frank.data());
+        return d;
+      })
       .def("set_step", &LREngine::set_step)
       .def("synchronize", &LREngine::synchronize)
       .def_property_readonly("num_weights", &LREngine::num_weights)

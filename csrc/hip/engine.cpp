@@ -393,6 +393,7 @@ void LREngine::alloc_prepared(PrepBuf& b) {
   b.host_norm.alloc(2 * sizeof(int64_t), hipHostMallocDefault);
   b.ev_start = Event(hipEventDefault);
   b.ev_done = Event(hipEventDefault);
+  b.ev_flag = Event(hipEventDisableTiming);
   if (dp_) {
     b.host_hdr.alloc(sizeof(int64_t) * size_t(world_) * (kC1HeaderWords / 2), hipHostMallocDefault);
     b.host_bounds.alloc(sizeof(double) * kBoundsLen, hipHostMallocDefault);
@@ -428,6 +429,7 @@ void LREngine::ensure_tier(PrepBuf& b, int64_t n_unique, hipStream_t s) {
   if (!p.fslot) {
     const size_t E = size_t(p.cap_entries);
     p.fslot = b.arena.alloc<uint32_t>(E);
+    p.frank = b.arena.alloc<uint32_t>(E);
     p.fcsc = b.arena.alloc<uint2>(E);
     p.fcount = b.arena.alloc<int32_t>(size_t(p.cap_chunks) + 1);
     p.hist_near = b.arena.alloc<uint32_t>(kMaxHybridSlots);
@@ -444,7 +446,7 @@ void LREngine::ensure_tier(PrepBuf& b, int64_t n_unique, hipStream_t s) {
   b.arena.grow(p.tscan, size_t(cap) + 1 + 2048, nullptr);   // + 4096 u32 count buckets
   b.arena.grow(p.tscan_blk, size_t(cap) / 2048 + 4, nullptr);   // multi-block scan tiles of 2048
   b.arena.grow(p.fhist, size_t(cap) + 1, nullptr);
-  b.arena.grow(p.fcur, size_t(cap) + 1, nullptr);
+  b.arena.grow(p.foff, size_t(cap) + 1, nullptr);
   if (cap + kNumNumeric + 64 > b.slot_hist_cap) {
     b.slot_hist_cap = cap + kNumNumeric + 64;
     b.arena.grow(p.slot_hist, size_t(b.slot_hist_cap), nullptr);
@@ -908,6 +910,12 @@ void LREngine::finish_layout(PrepBuf& pb, hipStream_t s, bool dp_hist) {
   if (prep.dedup) launch_dedup(prep, ns, kNumNumeric + nU, res.n_kept, s);
   res.n_near = pb.n_near;
   TWTML_HIP_CHECK(hipEventRecord(pb.ev_done, s));
+  if (tiered) {
+    // k_far_csc's position check (counters[3]): copied behind ev_done, off the
+    // batch's critical path, and read by train() after the batch's last sync
+    TWTML_HIP_CHECK(hipMemcpyAsync(pb.host_counters + 3, prep.counters + 3, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    TWTML_HIP_CHECK(hipEventRecord(pb.ev_flag, s));
+  }
   pb.stage = 2;
 }
 
@@ -1080,6 +1088,10 @@ BatchResult LREngine::train(PrepBuf& pb, bool want_pred, int64_t plot_points) {
   TWTML_HIP_CHECK(hipStreamSynchronize(s));
   th[3] = Clk::now();
   if (comm_) comm_->check_async();
+  if (tiered) {
+    TWTML_HIP_CHECK(hipEventSynchronize(pb.ev_flag));   // recorded before this batch's GD began
+    if (pb.host_counters[3] != 0) throw std::runtime_error("far CSC: entry position out of range");
+  }
   if (P > 0) {
     res.pred.resize(P);
     res.real.resize(P);
@@ -1651,6 +1663,55 @@ void LREngine::debug_prepared(std::vector<int64_t>& counters, std::vector<int32_
     TWTML_HIP_CHECK(hipMemcpy(idx.data(), lp.idx, sizeof(int32_t) * idx.size(), hipMemcpyDeviceToHost));
   if (nu)
     TWTML_HIP_CHECK(hipMemcpy(uniq.data(), lp.uniq, sizeof(int32_t) * size_t(nu), hipMemcpyDeviceToHost));
+}
+
+void LREngine::debug_far_layout(FarLayoutDebug& d) const {
+  TWTML_HIP_CHECK(hipSetDevice(device_));
+  TWTML_HIP_CHECK(hipStreamSynchronize(compute_));
+  TWTML_HIP_CHECK(hipStreamSynchronize(pstream_));
+  const DevPrepared& lp = pb_[last_buf_ < 0 ? 0 : last_buf_].dp;
+  d = FarLayoutDebug{};
+  if (!lp.tiered || !lp.fslot) return;
+  d.tiered = true;
+  int64_t counters[4], tparam[4];
+  TWTML_HIP_CHECK(hipMemcpy(counters, lp.counters, sizeof(counters), hipMemcpyDeviceToHost));
+  TWTML_HIP_CHECK(hipMemcpy(tparam, lp.tparam, sizeof(tparam), hipMemcpyDeviceToHost));
+  const int64_t C = (counters[0] + kRowsPerChunk - 1) / kRowsPerChunk;
+  const int64_t E = counters[2] * kChunkStride;
+  const int64_t n_far = kNumNumeric + counters[1] - lp.near_end;
+  d.near_end = lp.near_end;
+  d.far_total = tparam[2];
+  d.offsets.resize(size_t(n_far) + 1);
+  if (n_far > 0)
+    TWTML_HIP_CHECK(hipMemcpy(d.offsets.data(), lp.foff, sizeof(int64_t) * size_t(n_far), hipMemcpyDeviceToHost));
+  d.offsets[size_t(n_far)] = d.far_total;
+  const int64_t T = std::max<int64_t>(0, std::min<int64_t>(d.far_total, lp.cap_entries));
+  std::vector<uint2> csc(static_cast<size_t>(T));
+  if (T) TWTML_HIP_CHECK(hipMemcpy(csc.data(), lp.fcsc, sizeof(uint2) * size_t(T), hipMemcpyDeviceToHost));
+  d.csc_pos.resize(size_t(T));
+  d.csc_slot.resize(size_t(T));
+  for (int64_t i = 0; i < T; ++i) {
+    d.csc_pos[size_t(i)] = csc[size_t(i)].x;
+    d.csc_slot[size_t(i)] = csc[size_t(i)].y;
+  }
+  d.fcount.resize(size_t(C));
+  d.cbase.resize(size_t(C));
+  if (C) {
+    TWTML_HIP_CHECK(hipMemcpy(d.fcount.data(), lp.fcount, sizeof(int32_t) * size_t(C), hipMemcpyDeviceToHost));
+    TWTML_HIP_CHECK(hipMemcpy(d.cbase.data(), lp.cbase, sizeof(int64_t) * size_t(C), hipMemcpyDeviceToHost));
+  }
+  // the chunks' lists and ranks, concatenated in chunk order (fcount[c] each)
+  std::vector<uint32_t> fl(static_cast<size_t>(E)), fr(static_cast<size_t>(E));
+  if (E) {
+    TWTML_HIP_CHECK(hipMemcpy(fl.data(), lp.fslot, sizeof(uint32_t) * size_t(E), hipMemcpyDeviceToHost));
+    TWTML_HIP_CHECK(hipMemcpy(fr.data(), lp.frank, sizeof(uint32_t) * size_t(E), hipMemcpyDeviceToHost));
+  }
+  for (int64_t c = 0; c < C; ++c) {
+    const int64_t b = d.cbase[size_t(c)] * kChunkStride;
+    const int64_t n = std::max<int64_t>(0, std::min<int64_t>(d.fcount[size_t(c)], E - b));
+    d.flist.insert(d.flist.end(), fl.begin() + b, fl.begin() + b + n);
+    d.frank.insert(d.frank.end(), fr.begin() + b, fr.begin() + b + n);
+  }
 }
 
 }  // namespace twtml

@@ -216,6 +216,7 @@ struct PrepBuf {
   double* bounds = nullptr;           // device [kBoundsLen] batch bounds of the fixed-point scales
                                       // (DP: the max over ranks)
   Event ev_start, ev_done;
+  Event ev_flag;                      // prep stream, after the copy of the far-CSC position flag (tiered)
   // guarded by LREngine::mu_
   int state = 0;                      // 0 free, 1 being prepared, 2 prepared
   int slot = -1;
@@ -230,6 +231,17 @@ struct PrepBuf {
   int64_t row_offset = 0;             // global index of this rank's first kept row
   bool u16 = true;
   int64_t ns = 0, nl = 0, n_near = 0, far_base = 0;
+};
+
+// debug_far_layout(): host copies of the last prepared batch's far tier.
+struct FarLayoutDebug {
+  bool tiered = false;
+  int64_t near_end = 0, far_total = 0;   // first far slot; entries in the CSC (tparam[2])
+  std::vector<int64_t> offsets;          // [n_far + 1] CSC offset of far slot near_end + i, then the total
+  std::vector<uint32_t> csc_pos, csc_slot;   // [far_total] CSC pairs: sorted row position, slot
+  std::vector<int32_t> fcount;           // [C] far entries per chunk
+  std::vector<int64_t> cbase;            // [C] chunk bases (groups): chunk c's list starts at cbase[c] * 512
+  std::vector<uint32_t> flist, frank;    // the chunks' lists (row << 28 | slot) and ranks, concatenated
 };
 
 class LREngine {
@@ -295,10 +307,11 @@ class LREngine {
   int raw_slots() const { return raw_.count(); }
   int64_t lazy_bytes() const {
     const int nbuf = overlap_ ? 2 : 1;
-    // + the slot-sized tier arrays (newslot, slot_fid, tscan, fhist, fcur,
-    // slot_hist: 36 B per slot of active_set_hint())
-    return int64_t(nbuf) * 3 * int64_t(sizeof(uint32_t)) * pb_[0].dp.cap_entries +
-           (pb_[0].dp.cap_tier ? 0 : int64_t(nbuf) * 36 * active_set_hint()) +
+    // per entry: far list, ranks (4 B each) and CSC (8 B); + the slot-sized
+    // tier arrays (newslot, slot_fid, tscan, fhist, foff, slot_hist: 32 B per
+    // slot of active_set_hint())
+    return int64_t(nbuf) * 4 * int64_t(sizeof(uint32_t)) * pb_[0].dp.cap_entries +
+           (pb_[0].dp.cap_tier ? 0 : int64_t(nbuf) * 32 * active_set_hint()) +
            int64_t(sizeof(float)) * pb_[0].dp.cap_rows16 +
            (snap_idx_ ? 0 : 2 * num_weights() * int64_t(sizeof(int32_t) + sizeof(double)));
   }
@@ -335,6 +348,8 @@ class LREngine {
   // Hybrid dense-hot layout of the last batch (empty if not used).
   void debug_hybrid(std::vector<int32_t>& hot_slot, std::vector<uint32_t>& hot_dense,
                     std::vector<int32_t>& clen8c, std::vector<int32_t>& cslot) const;
+  // Far tier of the last batch (tiered stays false if it was not tiered).
+  void debug_far_layout(FarLayoutDebug& d) const;
 
  private:
   void alloc_prepared(PrepBuf& b);

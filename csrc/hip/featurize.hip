@@ -67,13 +67,13 @@ __device__ __forceinline__ int64_t block_prefix_of_sums(const int64_t* ts, int64
 }
 
 // Block b scans [b * span, min(n, (b + 1) * span)) starting from the sum of
-// tile_sums[0, b) (0 without tile_sums); single block: span = n.  out2, if
-// given, receives the same values.  total: the grand total (written by the
-// last block).
-template <int BT>
-__global__ __launch_bounds__(BT) void k_scan_excl(const int64_t* in, int64_t* out, int64_t n,
+// tile_sums[0, b) (0 without tile_sums); single block: span = n.  total: the
+// grand total (written by the last block).  TIn: int64_t (in place safe), or
+// uint32_t counts widened in the load (the far counts of the tiered layout).
+template <int BT, typename TIn>
+__global__ __launch_bounds__(BT) void k_scan_excl(const TIn* in, int64_t* out, int64_t n,
                                                   int64_t* total, const int64_t* tile_sums = nullptr,
-                                                  int64_t span = 0, int64_t* out2 = nullptr) {
+                                                  int64_t span = 0) {
   constexpr int kTile = BT * kScanPer;
   constexpr int kW = BT / 64;
   __shared__ int64_t tile_v[kTile + kTile / 32];   // +1 word per 32: fewer bank conflicts
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(BT) void k_scan_excl(const int64_t* in, int64_t* ou
 #pragma unroll
     for (int k = 0; k < kScanPer; ++k) {
       const int64_t i = base + k * BT + tid;
-      tile_v[at(k * BT + tid)] = i < b1 ? in[i] : 0;
+      tile_v[at(k * BT + tid)] = i < b1 ? int64_t(in[i]) : 0;
     }
     __syncthreads();
     int64_t v[kScanPer];
@@ -122,11 +122,7 @@ __global__ __launch_bounds__(BT) void k_scan_excl(const int64_t* in, int64_t* ou
 #pragma unroll
     for (int k = 0; k < kScanPer; ++k) {
       const int64_t i = base + k * BT + tid;
-      if (i < b1) {
-        const int64_t v = tile_v[at(k * BT + tid)];
-        out[i] = v;
-        if (out2) out2[i] = v;
-      }
+      if (i < b1) out[i] = tile_v[at(k * BT + tid)];
     }
     carry += tot;
     __syncthreads();
@@ -135,15 +131,15 @@ __global__ __launch_bounds__(BT) void k_scan_excl(const int64_t* in, int64_t* ou
 }
 
 // Tile sums for the multi-block scan: block b sums in[b * tile, ...).
-template <int BT>
-__global__ __launch_bounds__(BT) void k_tile_sum(const int64_t* in, int64_t n, int64_t* tsum) {
+template <int BT, typename TIn>
+__global__ __launch_bounds__(BT) void k_tile_sum(const TIn* in, int64_t n, int64_t* tsum) {
   __shared__ int64_t wsum[BT / 64];
   int64_t v = 0;
   const int64_t b0 = int64_t(blockIdx.x) * (BT * kScanPer);
 #pragma unroll
   for (int k = 0; k < kScanPer; ++k) {
     const int64_t i = b0 + k * BT + threadIdx.x;
-    v += i < n ? in[i] : 0;
+    v += i < n ? int64_t(in[i]) : 0;
   }
   v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
@@ -155,29 +151,34 @@ __global__ __launch_bounds__(BT) void k_tile_sum(const int64_t* in, int64_t n, i
   }
 }
 
-static void scan_excl(const int64_t* in, int64_t* out, int64_t n, int64_t* total, hipStream_t s,
-                      int64_t* out2 = nullptr) {
-  TWTML_LAUNCH(k_scan_excl<1024>, dim3(1), dim3(1024), 0, s, in, out, n, total, nullptr, int64_t(0), out2);
+template <typename TIn>
+static void scan_excl(const TIn* in, int64_t* out, int64_t n, int64_t* total, hipStream_t s) {
+  TWTML_LAUNCH((k_scan_excl<1024, TIn>), dim3(1), dim3(1024), 0, s, in, out, n, total, nullptr, int64_t(0));
 }
 
 // Multi-block exclusive scan (in place safe): tile sums, then every tile
 // scanned from the sum of the tile sums before it -- two launches.
 // tsum: ceil(n / kScanTileBig) + 1.
-static void scan_excl_big(const int64_t* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum,
-                          hipStream_t s, int64_t* out2 = nullptr) {
+template <typename TIn>
+static void scan_excl_big(const TIn* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum,
+                          hipStream_t s) {
   if (n <= kScanTile) {
-    scan_excl(in, out, n, total, s, out2);
+    scan_excl(in, out, n, total, s);
     return;
   }
   const int tiles = int((n + kScanTileBig - 1) / kScanTileBig);
-  TWTML_LAUNCH(k_tile_sum<kScanBT>, dim3(tiles), dim3(kScanBT), 0, s, in, n, tsum);
-  TWTML_LAUNCH(k_scan_excl<kScanBT>, dim3(tiles), dim3(kScanBT), 0, s, in, out, n, total,
-                     static_cast<const int64_t*>(tsum), int64_t(kScanTileBig), out2);
+  TWTML_LAUNCH((k_tile_sum<kScanBT, TIn>), dim3(tiles), dim3(kScanBT), 0, s, in, n, tsum);
+  TWTML_LAUNCH((k_scan_excl<kScanBT, TIn>), dim3(tiles), dim3(kScanBT), 0, s, in, out, n, total,
+                     static_cast<const int64_t*>(tsum), int64_t(kScanTileBig));
 }
 
-void launch_scan_excl(const int64_t* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum, hipStream_t s,
-                      int64_t* out2) {
-  scan_excl_big(in, out, n, total, tsum, s, out2);
+void launch_scan_excl(const int64_t* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum, hipStream_t s) {
+  scan_excl_big(in, out, n, total, tsum, s);
+}
+
+void launch_scan_excl_u32(const uint32_t* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum,
+                          hipStream_t s) {
+  scan_excl_big(in, out, n, total, tsum, s);
 }
 
 void scan_excl_launch(const int64_t* in, int64_t* out, int64_t n, int64_t* total, hipStream_t s) {

@@ -207,7 +207,15 @@ __global__ __launch_bounds__(1024) void k_code_tag(DevPrepared p, int64_t n_uniq
 //   text    (from_text) fast chunks re-derive their ids from the raw text
 //           (narrow_text.h) instead of reading idx
 //   far     (TIERED) entries of far slots go to the chunk's far list
-//           (row << 28 | slot, at cbase * 512 ..) and count into fhist
+//           (row << 28 | slot, at cbase * 512 ..).  Once the chunk's list is
+//           complete the wave counts it into fhist, one lane per entry: the
+//           returning add is the entry's rank inside its slot, kept in frank
+//           at the entry's list index.  k_far_csc places the entry at
+//           foff[slot] + rank, so the CSC build needs no second atomic.  The
+//           adds are issued together after the entry loop (no load or gather
+//           waits behind them) and the first 64 ranks are stored a chunk
+//           later (after the loop for the wave's last chunk), so the wave
+//           does not wait for the adds to return.
 // NW waves per workgroup (the code table is loaded once per workgroup): 4,
 // or 8 with a 6-waves-per-SIMD register budget (TWTML_REMAP_WAVES=8, A/B)
 template <bool TIERED, int NW>
@@ -220,6 +228,7 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(NW =
   __shared__ uint32_t cnt[NW][kRowsPerChunk * kCntStride];
   __shared__ uint32_t ccnt[NW][kRowsPerChunk];
   __shared__ uint32_t fcnt[NW];
+  __shared__ uint32_t fstage[TIERED ? NW : 1][kWave];   // the chunk's first 64 far entries (the rank pass reads them)
   for (int i = threadIdx.x; i < kCodeIds / 8; i += NW * kWave)
     reinterpret_cast<uint4*>(lcode)[i] = reinterpret_cast<const uint4*>(code)[i];
   __syncthreads();
@@ -241,6 +250,15 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(NW =
   const int64_t c_end = nch < fp.c_hi ? nch : fp.c_hi;   // this launch's chunk slice
   const int64_t c_first = fp.c_lo + wave;
   int64_t rt_next = (from_text && c_first < c_end) ? p.rtext[c_first * kRowsPerChunk + lane / kLanesPerRow] : 0;
+  // TIERED: the rank of the last chunk's far entry `lane`, stored one chunk
+  // later (its count atomic then has a chunk's time to return instead of
+  // stalling the wave), and after the loop
+  uint32_t pend_rk = 0u, pend_fc = 0u;
+  uint32_t* pend_frank = nullptr;
+  auto far_rank_flush = [&]() {
+    if (uint32_t(lane) < pend_fc) pend_frank[lane] = pend_rk;
+    pend_fc = 0u;
+  };
   for (int64_t c = c_first; c < c_end; c += nwaves) {
     const int64_t rt = rt_next;
     if (from_text && c + nwaves < c_end) rt_next = p.rtext[(c + nwaves) * kRowsPerChunk + lane / kLanesPerRow];
@@ -248,15 +266,33 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(NW =
     const int64_t off = p.cbase[c] * kChunkStride + lane * kGroup;
     const int32_t* src = p.idx + off;
     uint32_t* flist = TIERED ? p.fslot + p.cbase[c] * kChunkStride : nullptr;
+    uint32_t* frank = TIERED ? p.frank + p.cbase[c] * kChunkStride : nullptr;
     if (TIERED) {
       if (lane == 0) fcnt[w] = 0u;
       wave_lds_sync();
     }
     auto far_put = [&](uint32_t cd) {   // TIERED: far entry of row r -> the chunk's far list
-      const uint32_t sl = cd & kTagSlot;
+      const uint32_t e = (uint32_t(r) << 28) | (cd & kTagSlot);
       const uint32_t k = atomicAdd(&fcnt[w], 1u);
-      flist[k] = (uint32_t(r) << 28) | sl;
-      atomicAdd(reinterpret_cast<unsigned long long*>(&p.fhist[sl - near_end]), 1ull);
+      flist[k] = e;
+      if (k < uint32_t(kWave)) fstage[w][k] = e;
+    };
+    // TIERED, after a wave_lds_sync() behind the last far_put: one count
+    // atomic per list entry, returning the entry's rank.  Entries from 64 on
+    // (rare) are read back from the list and their ranks stored at once; the
+    // rank of entry `lane` stays pending until far_rank_flush.
+    auto far_rank_count = [&](uint32_t fc) {
+      far_rank_flush();   // the chunk before
+      uint32_t rk = 0u;
+      if (uint32_t(lane) < fc) rk = atomicAdd(&p.fhist[(fstage[w][lane] & kTagSlot) - near_end], 1u);
+      if (fc > uint32_t(kWave)) {   // wave-uniform
+        __threadfence_block();      // the list stores of this wave's other lanes
+        for (uint32_t k = uint32_t(kWave + lane); k < fc; k += uint32_t(kWave))
+          frank[k] = atomicAdd(&p.fhist[(flist[k] & kTagSlot) - near_end], 1u);
+      }
+      pend_rk = rk;
+      pend_fc = fc;
+      pend_frank = frank;
     };
     if (L8 > kMaxRegGroups) {   // plain layout (as k_remap)
       for (int32_t g = 0; g < L8; ++g) {
@@ -284,7 +320,9 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(NW =
       }
       if (TIERED) {
         wave_lds_sync();
-        if (lane == 0) p.fcount[c] = int32_t(fcnt[w]);
+        const uint32_t fc = fcnt[w];
+        far_rank_count(fc);
+        if (lane == 0) p.fcount[c] = int32_t(fc);
       }
       if (lane == 0) p.clen8c[c] = -1;
       continue;
@@ -345,6 +383,13 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(NW =
       }
     }
     wave_lds_sync();
+    // the far list is complete (the rare pass below adds cold entries only):
+    // its count atomics go out now
+    if (TIERED) {
+      const uint32_t fc = fcnt[w];
+      far_rank_count(fc);
+      if (lane == 0) p.fcount[c] = int32_t(fc);
+    }
     // dense part: this lane's 32 hot ids of its row; counts > 15 stay cold
     uint32_t nib[4] = {0u, 0u, 0u, 0u};
     bool ovf = false;
@@ -392,7 +437,6 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(NW =
       }
     }
     wave_lds_sync();   // every cold entry of the chunk is counted
-    if (TIERED && lane == 0) p.fcount[c] = int32_t(fcnt[w]);
     const uint32_t rc = ccnt[w][r];
     const int32_t mine = rc > uint32_t(t) ? int32_t((rc - uint32_t(t) + 3u) >> 2) : 0;   // this lane's entries
     const int32_t L4c = wave_max((mine + kColdGroup - 1) / kColdGroup);
@@ -402,6 +446,7 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(NW =
     if (lane == 0) p.clen8c[c] = L4c;
     wave_lds_sync();   // the next chunk clears / refills this wave's LDS
   }
+  if (TIERED) far_rank_flush();   // every listed entry has its rank when the kernel ends
 }
 
 
@@ -588,7 +633,12 @@ __global__ __launch_bounds__(1024) void k_code_tag_tiered(DevPrepared p, int64_t
   p.slot_of[id] = int32_t(tag);
 }
 
-// Far CSC: every far entry of every chunk list -> its slot's segment.
+// Far CSC: every far entry of every chunk list -> its slot's segment, at the
+// slot's offset plus the rank the remap's count atomic gave the entry (no
+// atomic here; the order inside a segment is the order of those counts, and
+// the integer slot sums of k_far_grad are exact in any order).  A position
+// outside [0, far total) would be a stray 8-byte store: it raises the
+// capacity flag (counters[3], an exception on the host) and is skipped.
 __global__ __launch_bounds__(256) void k_far_csc(DevPrepared p, int64_t c_lo, int64_t c_hi) {
   const int lane = lane_id();
   const int64_t n_kept = p.counters[0];
@@ -596,14 +646,18 @@ __global__ __launch_bounds__(256) void k_far_csc(DevPrepared p, int64_t c_lo, in
   const int64_t wave = (int64_t(blockIdx.x) * 256 + threadIdx.x) / kWave;
   const int64_t nwaves = int64_t(gridDim.x) * 256 / kWave;
   const uint32_t near_end = uint32_t(p.near_end);
+  const int64_t total = p.tparam[2];
   for (int64_t c = c_lo + wave; c < nch && c < c_hi; c += nwaves) {
     const int32_t fc = p.fcount[c];
-    const uint32_t* fl = p.fslot + p.cbase[c] * kChunkStride;
+    const int64_t base = p.cbase[c] * kChunkStride;
+    const uint32_t* fl = p.fslot + base;
+    const uint32_t* fr = p.frank + base;
     for (int32_t k = lane; k < fc; k += kWave) {
       const uint32_t e = fl[k];
       const uint32_t sl = e & kTagSlot;
-      const uint64_t at = atomicAdd(reinterpret_cast<unsigned long long*>(&p.fcur[sl - near_end]), 1ull);
-      p.fcsc[at] = make_uint2(uint32_t(c * kRowsPerChunk + (e >> 28)), sl);
+      const int64_t at = p.foff[sl - near_end] + int64_t(fr[k]);
+      if (at >= 0 && at < total) p.fcsc[at] = make_uint2(uint32_t(c * kRowsPerChunk + (e >> 28)), sl);
+      else p.counters[3] = 1;
     }
   }
 }
@@ -684,12 +738,12 @@ int64_t tier_near_cap() {
   return 0;
 }
 
-__global__ __launch_bounds__(1024) void k_tier_zero(uint32_t* buckets, uint32_t* hist_near, uint64_t* fhist,
+__global__ __launch_bounds__(1024) void k_tier_zero(uint32_t* buckets, uint32_t* hist_near, uint32_t* fhist,
                                                     int64_t n_fhist) {
   const int64_t i0 = int64_t(blockIdx.x) * 1024 + threadIdx.x, st = int64_t(gridDim.x) * 1024;
   for (int64_t i = i0; i < kCountBuckets; i += st) buckets[i] = 0u;
   for (int64_t i = i0; i < kMaxHybridSlots; i += st) hist_near[i] = 0u;
-  for (int64_t i = i0; i < n_fhist; i += st) fhist[i] = 0ull;
+  for (int64_t i = i0; i < n_fhist; i += st) fhist[i] = 0u;
 }
 
 void launch_tier_layout(const DevPrepared& p, int64_t entries, int64_t n_unique, int64_t n_near, int64_t ns,
@@ -723,10 +777,9 @@ void launch_tier_layout(const DevPrepared& p, int64_t entries, int64_t n_unique,
     const int64_t cmax = (p.cap_rows + kRowsPerChunk - 1) / kRowsPerChunk;
     launch_remap_slices<true>(p, ns, p.near_end, cmax, num_cu, b, fp, from_text, s);
   }
-  // CSC offsets (exclusive scan of the far counts, in place), cursors, scatter
-  // CSC offsets, and the scatter cursors as a second copy of them
-  launch_scan_excl(reinterpret_cast<const int64_t*>(p.fhist), reinterpret_cast<int64_t*>(p.fhist), n_far,
-                   p.tparam + 2, p.tscan_blk, s, reinterpret_cast<int64_t*>(p.fcur));
+  // CSC offsets (exclusive scan of the far counts, far total in tparam[2]),
+  // then the scatter to offset + rank
+  launch_scan_excl_u32(p.fhist, p.foff, n_far, p.tparam + 2, p.tscan_blk, s);
   if (entries > 0) {
     const int64_t cmax = (p.cap_rows + kRowsPerChunk - 1) / kRowsPerChunk;
     const int nsl = prep_slices();

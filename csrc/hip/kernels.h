@@ -173,9 +173,11 @@ struct DevPrepared {
   int32_t tiered;
   int64_t near_end;
   uint32_t* fslot;          // [E] far entries of chunk c from cbase[c] * 512 on
+  uint32_t* frank;          // [E] rank of far entry k of chunk c inside its slot (what the remap's count
+                            //     atomic returned), at the same index as fslot: CSC position = foff + rank
   int32_t* fcount;          // [C] far entries per chunk
-  uint64_t* fhist;          // [cap_tier + 1] entries per far slot, scanned in place into CSC offsets
-  uint64_t* fcur;           // [cap_tier] CSC scatter cursors
+  uint32_t* fhist;          // [cap_tier + 1] entries per far slot (counted by the remap)
+  int64_t* foff;            // [cap_tier + 1] CSC offsets: the exclusive scan of fhist
   uint2* fcsc;              // [E] CSC: (sorted position of the entry's row, far slot) -- one 8-B scattered store
   int32_t* newslot;         // [cap_tier] compact index u -> slot
   int32_t* slot_fid;        // [cap_tier + 64] slot -> feature id
@@ -285,8 +287,10 @@ void launch_eval(const DevRawBatch& b, const double* pred, const int64_t* rows, 
                  hipStream_t s);
 
 // Exclusive int64 scan (in place safe); tsum: ceil(n / 2048) + 2 scratch.
-void launch_scan_excl(const int64_t* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum, hipStream_t s,
-                      int64_t* out2 = nullptr);
+void launch_scan_excl(const int64_t* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum, hipStream_t s);
+// The same over uint32_t counts, widened in the scan's load (out of place).
+void launch_scan_excl_u32(const uint32_t* in, int64_t* out, int64_t n, int64_t* total, int64_t* tsum,
+                          hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Tiered layout (tiered.hip), in place of launch_remap_hybrid when the active

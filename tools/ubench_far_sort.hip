@@ -1,8 +1,13 @@
 // Far CSC build, micro-benchmark (alone on the GPU): n (row, slot) entries
 // grouped by slot
-//   (a) the engine's way: a 64-bit cursor atomic per entry + a scattered
-//       8-byte store (k_far_csc, hot_split.hip), cursors from a prior scan;
-//   (b) rocprim::radix_sort_pairs on the slot bits (key = slot, value = row).
+//   (a) the engine's way up to r10: a 64-bit cursor atomic per entry + a
+//       scattered 8-byte store, cursors from a prior scan;
+//   (b) rocprim::radix_sort_pairs on the slot bits (key = slot, value = row);
+//   (c) the rank scheme (k_far_csc, hot_split.hip, from r11): the count pass (the remap's per-entry count atomic)
+//       returns the entry's rank inside its slot, 32- or 64-bit counters, and
+//       the scatter is out[offset[slot] + rank] with no atomic.  The present
+//       scheme's count pass (non-returning 64-bit adds) is timed too, so both
+//       schemes are compared as count pass + scatter.
 // hipcc -O3 --offload-arch=gfx950 -I/opt/rocm/include tools/ubench_far_sort.hip -o /tmp/ubfs
 #include <hip/hip_runtime.h>
 
@@ -47,6 +52,29 @@ __global__ void k_atomics_only(const uint32_t* slot, int64_t n, unsigned long lo
     const uint32_t s = slot[i];
     const unsigned long long at = atomicAdd(&cur[s], 1ull);
     out[i] = make_uint2(uint32_t(at), s);
+  }
+}
+
+// count pass of the present scheme: a non-returning 64-bit add per entry
+__global__ void k_count64(const uint32_t* slot, int64_t n, unsigned long long* cnt) {
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x)
+    atomicAdd(&cnt[slot[i]], 1ull);
+}
+
+// count pass of the rank scheme: the add returns the entry's rank (coalesced store)
+template <typename T>
+__global__ void k_count_rank(const uint32_t* slot, int64_t n, T* cnt, uint32_t* rank) {
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x)
+    rank[i] = uint32_t(atomicAdd(&cnt[slot[i]], T(1)));
+}
+
+// scatter of the rank scheme: no atomic; a position beyond the total is skipped
+__global__ void k_scatter_rank(const uint32_t* slot, const uint32_t* row, const uint32_t* rank, int64_t n,
+                               const unsigned long long* off, uint2* out) {
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
+    const uint32_t s = slot[i];
+    const unsigned long long at = off[s] + rank[i];
+    if (at < static_cast<unsigned long long>(n)) out[at] = make_uint2(row[i], s);
   }
 }
 
@@ -127,6 +155,61 @@ int main(int argc, char** argv) {
       if (r > 1) tot += ms;
     }
     std::printf("n %lld slots %u  32-bit atomic scatter   : %8.1f us\n", (long long)n, nslots, 1e3 * tot / (reps - 2));
+  }
+  {   // (c) rank scheme
+    uint32_t *rank, *c32;
+    unsigned long long* c64;
+    CK(hipMalloc(&rank, n * 4));
+    CK(hipMalloc(&c32, (nslots + 1) * 4));
+    CK(hipMalloc(&c64, (nslots + 1) * 8));
+    float t_cnt = 0, t_r64 = 0, t_r32 = 0, t_sc = 0;
+    for (int r = 0; r < reps; ++r) {
+      CK(hipMemset(c64, 0, (nslots + 1) * 8));
+      CK(hipEventRecord(a));
+      hipLaunchKernelGGL(k_count64, dim3(2048), dim3(256), 0, 0, ds, n, c64);
+      CK(hipEventRecord(b));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      if (r > 1) t_cnt += ms;
+      CK(hipMemset(c64, 0, (nslots + 1) * 8));
+      CK(hipEventRecord(a));
+      hipLaunchKernelGGL(k_count_rank<unsigned long long>, dim3(2048), dim3(256), 0, 0, ds, n, c64, rank);
+      CK(hipEventRecord(b));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      if (r > 1) t_r64 += ms;
+      CK(hipMemset(c32, 0, (nslots + 1) * 4));
+      CK(hipEventRecord(a));
+      hipLaunchKernelGGL(k_count_rank<uint32_t>, dim3(2048), dim3(256), 0, 0, ds, n, c32, rank);
+      CK(hipEventRecord(b));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      if (r > 1) t_r32 += ms;
+      CK(hipMemset(out, 0xFF, n * 8));
+      CK(hipEventRecord(a));
+      hipLaunchKernelGGL(k_scatter_rank, dim3(2048), dim3(256), 0, 0, ds, dr, rank, n, dc0, out);
+      CK(hipEventRecord(b));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      if (r > 1) t_sc += ms;
+    }
+    const double k = 1e3 / (reps - 2);
+    std::printf("n %lld slots %u  count, 64-bit no return : %8.1f us\n", (long long)n, nslots, k * t_cnt);
+    std::printf("n %lld slots %u  count, 64-bit -> rank   : %8.1f us\n", (long long)n, nslots, k * t_r64);
+    std::printf("n %lld slots %u  count, 32-bit -> rank   : %8.1f us\n", (long long)n, nslots, k * t_r32);
+    std::printf("n %lld slots %u  rank scatter (no atomic): %8.1f us\n", (long long)n, nslots, k * t_sc);
+    // check: every position written once, by an entry of the segment's slot
+    std::vector<uint2> ho(static_cast<size_t>(n));
+    CK(hipMemcpy(ho.data(), out, n * 8, hipMemcpyDeviceToHost));
+    bool rk_ok = true;
+    for (uint32_t s = 0; s < nslots && rk_ok; ++s)
+      for (unsigned long long i = hc[s]; i < hc[s + 1]; ++i)
+        if (ho[size_t(i)].y != s) {
+          rk_ok = false;
+          break;
+        }
+    std::printf("rank scatter grouped by slot %s\n", rk_ok ? "yes" : "NO");
+    if (!rk_ok) return 1;
   }
   int bits = 1;
   while ((1u << bits) < nslots) ++bits;

@@ -7,8 +7,8 @@ their decode tails, the prepared-batch entry streams, tier lists).  Rather
 than restating every allocation here, :func:`engine_footprint` builds two
 probe engines and reads the bytes they allocate
 (``_twtml_hip.device_bytes_allocated``) plus what an LR engine allocates on
-its first tiered batch (``lazy_bytes``: the entry-sized far lists and CSC of
-both prepared buffers, ~48 B per text unit of capacity), and
+its first tiered batch (``lazy_bytes``: the entry-sized far lists, ranks and
+CSC of both prepared buffers, ~64 B per text unit of capacity), and
 :func:`hbm_max_rows` solves for the largest capacity that fits a fraction of
 the GPU's free memory.  The remaining headroom covers the buffers that grow
 with a batch's active set (compact weights, slot-sized tier arrays: ~100 B
