@@ -337,6 +337,7 @@ LREngine::LREngine(int device, const LRConfig& cfg, std::shared_ptr<Comm> comm)
     hnu_.alloc(sizeof(int64_t) * size_t(world_), hipHostMallocDefault);
   }
   TWTML_HIP_CHECK(hipDeviceSynchronize());
+  handoff_ = std::make_unique<PrepHandoff>(overlap_, dp_, dp_ ? ready_host_.get() : nullptr);
   if (overlap_) worker_ = std::thread([this] { prep_worker(); });
 }
 
@@ -488,11 +489,7 @@ void LREngine::ensure_compact(int64_t ns) {
 }
 
 LREngine::~LREngine() {
-  {
-    std::lock_guard<std::mutex> lk(mu_);
-    stop_ = true;
-  }
-  cv_.notify_all();
+  if (handoff_) handoff_->shutdown();
   if (worker_.joinable()) worker_.join();
   (void)hipSetDevice(device_);
   // a fault of this engine's last work surfaces here: report it (and keep it
@@ -507,28 +504,25 @@ void LREngine::submit(const HostBatch& hb, int64_t n, int64_t bytes, int slot, c
                       int64_t now_ms, bool train) {
   TraceRange tr("twtml.lr.submit_h2d");
   TWTML_HIP_CHECK(hipSetDevice(device_));
-  std::lock_guard<std::mutex> lk(mu_);
   // a scoring batch must not land in a slot that a queued or prepared
   // training batch still owns
-  if (!train && training_owns_locked(slot))
+  if (!train && handoff_->owns(slot))
     throw std::logic_error("submit(train=false): the slot holds a batch queued or prepared for training");
   raw_.submit(hb, n, bytes, slot, copy_, kScalarCols, ext_text);
-  if (!train) return;   // score() only: never in the prepare-ahead queue
-  submitted_.push_back({slot, now_ms});
-  cv_.notify_all();
+  // score() only: never in the prepare-ahead queue; else queued once its H2D is
+  if (train) handoff_->enqueue(slot, now_ms);
+}
+
+// The filter / featurizer parameters of a batch with time now_ms;
+// apply_filter = false keeps every row.
+FeaturizeParams LREngine::featurize_params(int64_t now_ms, bool apply_filter) const {
+  return FeaturizeParams{cfg_.num_text_features, cfg_.hash_kind, apply_filter ? cfg_.require_retweet : 0,
+                         apply_filter ? cfg_.range_filter : 0, cfg_.begin, cfg_.end, now_ms};
 }
 
 // ---------------------------------------------------------------------------
 // Inference-only scoring (score.hip) on the compute stream.
 // ---------------------------------------------------------------------------
-// Caller holds mu_: `slot` is in the prepare-ahead queue or a prepared buffer.
-bool LREngine::training_owns_locked(int slot) const {
-  for (const auto& q : submitted_)
-    if (q.first == slot) return true;
-  for (const auto& b : pb_)
-    if (b.state != 0 && b.slot == slot) return true;
-  return false;
-}
 
 void LREngine::ensure_score() {
   if (score_out_) return;
@@ -555,32 +549,47 @@ void LREngine::ensure_score() {
   p.counters = score_out_;
 }
 
+// The pass score() and evaluate() share (engine.h ScorePass); the caller
+// records its end event, releases the raw slot and copies its results.
+bool LREngine::score_pass(const char* who, int slot, int64_t now_ms, bool apply_filter, int link, double link_thr,
+                          bool eval, ScorePass& p) {
+  if (handoff_->owns(slot))
+    throw std::logic_error(std::string(who) + ": the slot holds a batch queued or prepared for training");
+  p.n_raw = raw_.rows(slot);
+  if (p.n_raw == 0) return false;
+  if (eval) ensure_eval();
+  else ensure_score();
+  hipStream_t s = compute_;
+  p.b = raw_.acquire(slot, s);
+  const FeaturizeParams fp = featurize_params(now_ms, apply_filter);
+  p.pred = reinterpret_cast<double*>(score_out_ + 8);
+  p.rows = apply_filter ? score_out_ + 8 + p.b.n : nullptr;
+  TWTML_HIP_CHECK(hipEventRecord(eval ? eval_ev_[0] : score_ev_[0], s));
+  launch_score_init(score_dp_, s);
+  launch_filter_sort(p.b, score_dp_, fp, s);
+  launch_chunk_layout(p.b, score_dp_, s);
+  launch_score(p.b, score_dp_, fp, lower_page_, lower_blocks_, sgd_.w64, p.pred, p.rows, s, link, link_thr);
+  return true;
+}
+
+// the kept-row count a scoring pass brought back: within the batch, and all of it without the filter
+static void check_scored(const char* who, int64_t n_scored, int64_t n, bool apply_filter) {
+  if (n_scored < 0 || n_scored > n || (!apply_filter && n_scored != n))
+    throw std::runtime_error(std::string(who) + ": kept-row count out of range");
+}
+
 ScoreResult LREngine::score(int slot, int64_t now_ms, bool apply_filter, int link) {
   if (link < kLinkMargin || link > kLinkClass) throw std::invalid_argument("score(): unknown link");
   TraceRange tr("twtml.lr.score");
   TWTML_HIP_CHECK(hipSetDevice(device_));
   const auto t_in = std::chrono::steady_clock::now();
-  {
-    std::lock_guard<std::mutex> lk(mu_);
-    if (training_owns_locked(slot))
-      throw std::logic_error("score(): the slot holds a batch queued or prepared for training");
-  }
   ScoreResult res;
-  res.n_raw = raw_.rows(slot);
-  if (res.n_raw == 0) return res;
-  ensure_score();
+  ScorePass p;
+  const bool any = score_pass("score()", slot, now_ms, apply_filter, link, logit_threshold(), false, p);
+  res.n_raw = p.n_raw;
+  if (!any) return res;
   hipStream_t s = compute_;
-  const DevRawBatch b = raw_.acquire(slot, s);
-  const int64_t n = b.n;
-  FeaturizeParams fp{cfg_.num_text_features, cfg_.hash_kind, apply_filter ? cfg_.require_retweet : 0,
-                     apply_filter ? cfg_.range_filter : 0, cfg_.begin, cfg_.end, now_ms};
-  double* pred = reinterpret_cast<double*>(score_out_ + 8);
-  int64_t* rows = apply_filter ? score_out_ + 8 + n : nullptr;
-  TWTML_HIP_CHECK(hipEventRecord(score_ev_[0], s));
-  launch_score_init(score_dp_, s);
-  launch_filter_sort(b, score_dp_, fp, s);
-  launch_chunk_layout(b, score_dp_, s);
-  launch_score(b, score_dp_, fp, lower_page_, lower_blocks_, sgd_.w64, pred, rows, s, link, logit_threshold());
+  const int64_t n = p.b.n;
   TWTML_HIP_CHECK(hipEventRecord(score_ev_[1], s));
   raw_.release_slot(slot, s);   // the raw slot may be overwritten now
   const size_t words = 8 + size_t(apply_filter ? 2 * n : n);
@@ -588,8 +597,7 @@ ScoreResult LREngine::score(int slot, int64_t now_ms, bool apply_filter, int lin
   TWTML_HIP_CHECK(hipStreamSynchronize(s));
   const int64_t* h = score_host_.get();
   res.n_scored = h[0];
-  if (res.n_scored < 0 || res.n_scored > n || (!apply_filter && res.n_scored != n))
-    throw std::runtime_error("score(): kept-row count out of range");
+  check_scored("score()", res.n_scored, n, apply_filter);
   res.pred = reinterpret_cast<const double*>(h + 8);
   res.rows = apply_filter ? h + 8 + n : nullptr;
   TWTML_HIP_CHECK(hipEventElapsedTime(&res.score_ms, score_ev_[0], score_ev_[1]));
@@ -615,31 +623,16 @@ EvalResult LREngine::evaluate(int slot, int64_t now_ms, bool apply_filter) {
   TraceRange tr("twtml.lr.eval");
   TWTML_HIP_CHECK(hipSetDevice(device_));
   const auto t_in = std::chrono::steady_clock::now();
-  {
-    std::lock_guard<std::mutex> lk(mu_);
-    if (training_owns_locked(slot))
-      throw std::logic_error("evaluate(): the slot holds a batch queued or prepared for training");
-  }
   EvalResult res;
   res.binary = cfg_.loss == kLossLogistic;
-  res.n_raw = raw_.rows(slot);
-  if (res.n_raw == 0) return res;
-  ensure_eval();
+  ScorePass p;
+  const bool any = score_pass("evaluate()", slot, now_ms, apply_filter, kLinkMargin, 0.0, true, p);
+  res.n_raw = p.n_raw;
+  if (!any) return res;
   hipStream_t s = compute_;
-  const DevRawBatch b = raw_.acquire(slot, s);
-  const int64_t n = b.n;
-  FeaturizeParams fp{cfg_.num_text_features, cfg_.hash_kind, apply_filter ? cfg_.require_retweet : 0,
-                     apply_filter ? cfg_.range_filter : 0, cfg_.begin, cfg_.end, now_ms};
-  double* pred = reinterpret_cast<double*>(score_out_ + 8);
-  int64_t* rows = apply_filter ? score_out_ + 8 + n : nullptr;
   double* out_d = reinterpret_cast<double*>(eval_out_ + kEvalIntWords);
-  TWTML_HIP_CHECK(hipEventRecord(eval_ev_[0], s));
-  launch_score_init(score_dp_, s);
-  launch_filter_sort(b, score_dp_, fp, s);
-  launch_chunk_layout(b, score_dp_, s);
-  launch_score(b, score_dp_, fp, lower_page_, lower_blocks_, sgd_.w64, pred, rows, s, kLinkMargin, 0.0);
-  launch_eval(b, pred, rows, score_dp_.counters, res.binary ? cfg_.label_threshold : -1, logit_threshold(), eval_out_,
-              out_d, eval_part_, s);
+  launch_eval(p.b, p.pred, p.rows, score_dp_.counters, res.binary ? cfg_.label_threshold : -1, logit_threshold(),
+              eval_out_, out_d, eval_part_, s);
   TWTML_HIP_CHECK(hipEventRecord(eval_ev_[1], s));
   raw_.release_slot(slot, s);   // the raw slot may be overwritten now
   TWTML_HIP_CHECK(hipMemcpyAsync(eval_host_.get(), eval_out_, sizeof(int64_t) * (kEvalIntWords + kEvalF64Words),
@@ -647,8 +640,7 @@ EvalResult LREngine::evaluate(int slot, int64_t now_ms, bool apply_filter) {
   TWTML_HIP_CHECK(hipStreamSynchronize(s));
   const int64_t* h = eval_host_.get();
   res.n_scored = h[kEvalScored];
-  if (res.n_scored < 0 || res.n_scored > n || (!apply_filter && res.n_scored != n))
-    throw std::runtime_error("evaluate(): kept-row count out of range");
+  check_scored("evaluate()", res.n_scored, p.b.n, apply_filter);
   if (h[kEvalN] + h[kEvalNan] != res.n_scored)
     throw std::runtime_error("evaluate(): the accumulator does not hold every scored row");
   res.iw = h;
@@ -666,10 +658,20 @@ EvalResult LREngine::evaluate(int slot, int64_t now_ms, bool apply_filter) {
 // prepare_global_dp.
 // ---------------------------------------------------------------------------
 
+// Fault injection (tests): <env>=<rank>:<n> fails this rank's n-th call
+// (1-based, n = 1 if omitted) with `what`.  Ranks come from the communicator:
+// without one nothing is injected.
+void LREngine::inject_failure(const char* env, int& calls, const char* what) {
+  const char* f = std::getenv(env);
+  if (!f || !comm_) return;
+  int fr = -1, fn = 1;
+  if (std::sscanf(f, "%d:%d", &fr, &fn) >= 1 && fr == comm_->rank() && ++calls == fn) throw std::runtime_error(what);
+}
+
 // Local part (no collectives): decode / lower rows, filter, sort, chunk
 // layout, featurize, this rank's active set; ends with its counts on the
 // host.  DP: + the sampled counts of the local active ids and the packet.
-void LREngine::prepare_local(PrepBuf& pb, int slot, int64_t now_ms, hipStream_t s) {
+int64_t LREngine::prepare_local(PrepBuf& pb, int slot, int64_t now_ms, hipStream_t s) {
   TraceRange tr_prep("twtml.lr.prep");   // filter .. remap
   TWTML_HIP_CHECK(hipSetDevice(device_));
   const int world = world_;
@@ -679,16 +681,9 @@ void LREngine::prepare_local(PrepBuf& pb, int slot, int64_t now_ms, hipStream_t 
   const DevRawBatch b = raw_.acquire(slot, s);
   res.n_raw = b.n;
   TWTML_HIP_CHECK(hipEventRecord(pb.ev_start, s));
-  // fault injection (tests): TWTML_INJECT_PREP_FAIL=<rank>:<n> fails this
-  // rank's n-th local prep (1-based)
-  if (const char* f = std::getenv("TWTML_INJECT_PREP_FAIL")) {
-    int fr = -1, fn = 1;
-    if (std::sscanf(f, "%d:%d", &fr, &fn) >= 1 && comm_ && fr == comm_->rank() && ++prep_calls_ == fn)
-      throw std::runtime_error("injected prep failure");
-  }
+  inject_failure("TWTML_INJECT_PREP_FAIL", prep_calls_, "injected prep failure");
 
-  FeaturizeParams fp{cfg_.num_text_features, cfg_.hash_kind, cfg_.require_retweet,
-                     cfg_.range_filter, cfg_.begin, cfg_.end, now_ms};
+  FeaturizeParams fp = featurize_params(now_ms, true);
   fp.label_threshold = cfg_.label_threshold;
   launch_prep_init(prep, pb.n_global, 2 * world + 2, s, pb.bounds, kBoundsLen);
   launch_filter_sort(b, prep, fp, s);
@@ -710,10 +705,11 @@ void LREngine::prepare_local(PrepBuf& pb, int slot, int64_t now_ms, hipStream_t 
                                  hipMemcpyDeviceToHost, s));
   TWTML_HIP_CHECK(hipStreamSynchronize(s));
   if (pb.host_counters[3] != 0) throw std::runtime_error("feature buffer capacity exceeded");
+  int64_t nU = 0;
   if (dp_) {
     // the packet: sampled counts of the local active ids (the same sampled
     // chunks as the tiered near-tier choice), then header + (id, count) pairs
-    const int64_t nU = pb.host_counters[1];
+    nU = pb.host_counters[1];
     ensure_tier(pb, nU, s);
     if (nU > 0) {
       TWTML_HIP_CHECK(hipMemsetAsync(prep.slot_hist + kNumNumeric, 0, sizeof(uint32_t) * size_t(nU), s));
@@ -729,17 +725,15 @@ void LREngine::prepare_local(PrepBuf& pb, int slot, int64_t now_ms, hipStream_t 
     TWTML_HIP_CHECK(hipMemsetAsync(prep.slot_hist, 0,
                                    sizeof(uint32_t) * size_t(std::min<int64_t>(kNumNumeric + nU, pb.slot_hist_cap)), s));
     TWTML_HIP_CHECK(hipStreamSynchronize(s));
-    pb.nu_local = nU;
   }
   pb.raw = b;
   pb.fp = fp;
   pb.lazy = lazy;
-  pb.slot = slot;
-  pb.stage = 1;
+  return nU;
 }
 
 // One GPU: counts from the device, then the layout.
-void LREngine::prepare_global(PrepBuf& pb, hipStream_t s) {
+void LREngine::prepare_global(PrepBuf& pb, int slot, hipStream_t s) {
   TraceRange tr_prep("twtml.lr.prep_global");
   TWTML_HIP_CHECK(hipSetDevice(device_));
   const int64_t* hc = pb.host_counters;
@@ -751,19 +745,20 @@ void LREngine::prepare_global(PrepBuf& pb, hipStream_t s) {
   res.n_unique = hc[1];
   res.entries = hc[2] * kChunkStride;
   pb.row_offset = 0;
-  finish_layout(pb, s, false);
+  finish_layout(pb, slot, s, -1);
 }
 
 // DP: the all-gather of the ranks' packets, on the compute stream, between
 // two GD iterations of the previous batch (or in line, issue_c1_inline).
 // Every rank issues it at the same point of its collective sequence.
-void LREngine::issue_c1(PrepBuf& pb, int64_t max_u) {
+void LREngine::issue_c1(int buf, int64_t nu_local, int64_t max_u) {
   TraceRange tr("twtml.lr.prep_allgather");
+  PrepBuf& pb = pb_[buf];
   hipStream_t s = compute_;
   const int64_t pw = c1_packet_words(max_u);
   if (max_u > pb.pkt_cap) {   // another rank's active set is larger than this packet holds (rare)
     int32_t* np = pb.arena.alloc<int32_t>(size_t(pw));   // keeps its contents: copy, then free the old one
-    TWTML_HIP_CHECK(hipMemcpyAsync(np, pb.packet, sizeof(int32_t) * size_t(c1_packet_words(pb.nu_local)),
+    TWTML_HIP_CHECK(hipMemcpyAsync(np, pb.packet, sizeof(int32_t) * size_t(c1_packet_words(nu_local)),
                                    hipMemcpyDeviceToDevice, s));
     TWTML_HIP_CHECK(hipStreamSynchronize(s));
     pb.arena.free(pb.packet);
@@ -774,27 +769,23 @@ void LREngine::issue_c1(PrepBuf& pb, int64_t max_u) {
     pb.gath_cap = std::max<int64_t>(max_u + max_u / 4 + 1024, pb.gath_cap);
     pb.arena.grow(pb.gathered, size_t(world_) * size_t(c1_packet_words(pb.gath_cap)), s);
   }
-  if (max_u > pb.nu_local)   // pad this rank's pairs to the largest rank's: id -1
-    TWTML_HIP_CHECK(hipMemsetAsync(pb.packet + c1_packet_words(pb.nu_local), 0xFF,
-                                   sizeof(int32_t) * 2 * size_t(max_u - pb.nu_local), s));
+  if (max_u > nu_local)   // pad this rank's pairs to the largest rank's: id -1
+    TWTML_HIP_CHECK(hipMemsetAsync(pb.packet + c1_packet_words(nu_local), 0xFF,
+                                   sizeof(int32_t) * 2 * size_t(max_u - nu_local), s));
   comm_->allgather(pb.packet, pb.gathered, size_t(pw), ncclInt32, s);
   TWTML_HIP_CHECK(hipEventRecord(pb.ev_c1, s));
-  std::lock_guard<std::mutex> lk(mu_);
-  pb.c1_maxu = max_u;
-  pb.c1 = 2;
-  __atomic_store_n(ready_host_.get(), int64_t(0), __ATOMIC_RELEASE);
-  cv_.notify_all();
+  handoff_->gathered(buf, max_u);   // the ready word goes back to 0; the prep thread goes on
 }
 
 // DP, the packets were not gathered during the previous batch (first batch,
 // or the ranks' local parts finished after its GD loop): size the all-gather
 // with an all-reduce of one active-set size per rank, then gather.
-bool LREngine::issue_c1_inline(PrepBuf* pb) {
+int64_t LREngine::issue_c1_inline(int buf, int64_t nu_local) {
   hipStream_t s = compute_;
   const int rank = comm_->rank();
   // a rank whose local prep failed contributes -1: every rank then skips the
   // all-gather and raises, instead of the others blocking in it
-  for (int r = 0; r < world_; ++r) hnu_[r] = r == rank ? (pb ? pb->nu_local : int64_t(-1)) : 0;
+  for (int r = 0; r < world_; ++r) hnu_[r] = r == rank ? (buf >= 0 ? nu_local : int64_t(-1)) : 0;
   TWTML_HIP_CHECK(hipMemcpyAsync(dnu_, hnu_, sizeof(int64_t) * size_t(world_), hipMemcpyHostToDevice, s));
   comm_->allreduce(dnu_, size_t(world_), ncclInt64, ncclSum, s);
   TWTML_HIP_CHECK(hipMemcpyAsync(hnu_, dnu_, sizeof(int64_t) * size_t(world_), hipMemcpyDeviceToHost, s));
@@ -805,32 +796,25 @@ bool LREngine::issue_c1_inline(PrepBuf* pb) {
     mx = std::max(mx, hnu_[r]);
     ok = ok && hnu_[r] >= 0;
   }
-  if (ok && pb) issue_c1(*pb, mx);
-  return ok;
+  if (ok && buf >= 0) issue_c1(buf, nu_local, mx);
+  return ok ? mx : -1;
 }
 
 // DP global part, no collectives: per-rank kept rows (global m, sampling
 // offsets) and bounds from the gathered headers, the active-id union
 // (flags + compaction: every rank numbers the same slots), the union's
 // summed sampled counts (tiered near tier), then the layout.
-void LREngine::prepare_global_dp(PrepBuf& pb, hipStream_t s) {
+void LREngine::prepare_global_dp(PrepBuf& pb, int slot, int64_t max_u, hipStream_t s) {
   TraceRange tr_prep("twtml.lr.prep_global");
   TWTML_HIP_CHECK(hipSetDevice(device_));
   // A failure here (after the packet all-gather) raises on this rank only:
   // its peers go on into the batch's first gradient all-reduce and wait
   // there, and the batch watchdog (--batchTimeout; bench.py --timeout) or
   // the launcher tearing the group down after this rank's exit ends them.
-  // TWTML_INJECT_GLOBAL_PREP_FAIL=<rank>:<n> (tests) fails this rank's n-th
-  // global prep.
-  if (const char* f = std::getenv("TWTML_INJECT_GLOBAL_PREP_FAIL")) {
-    int fr = -1, fn = 1;
-    if (std::sscanf(f, "%d:%d", &fr, &fn) >= 1 && fr == comm_->rank() && ++gprep_calls_ == fn)
-      throw std::runtime_error("injected global prep failure");
-  }
+  inject_failure("TWTML_INJECT_GLOBAL_PREP_FAIL", gprep_calls_, "injected global prep failure");
   const int world = world_, rank = comm_->rank();
   DevPrepared& prep = pb.dp;
   BatchResult& res = pb.res;
-  const int64_t max_u = pb.c1_maxu;
   const int64_t pw = c1_packet_words(max_u);
   constexpr int kH = kC1HeaderWords / 2;   // int64 header words per rank
   TWTML_HIP_CHECK(hipStreamWaitEvent(s, pb.ev_c1, 0));
@@ -860,13 +844,13 @@ void LREngine::prepare_global_dp(PrepBuf& pb, hipStream_t s) {
   res.n_unique = hc[1];
   res.entries = hc[2] * kChunkStride;
   pb.row_offset = row_offset;
-  finish_layout(pb, s, true);
+  finish_layout(pb, slot, s, max_u);
 }
 
 // Compact space of the (global) active set and the hybrid / tiered layout.
-// dp_hist: slot counts for the tiered near tier from the gathered packets
+// dp_max_u >= 0: slot counts for the tiered near tier from the gathered packets
 // (every rank numbers the slots from the same counts), else sampled here.
-void LREngine::finish_layout(PrepBuf& pb, hipStream_t s, bool dp_hist) {
+void LREngine::finish_layout(PrepBuf& pb, int slot, hipStream_t s, int64_t dp_max_u) {
   DevPrepared& prep = pb.dp;
   BatchResult& res = pb.res;
   const DevRawBatch& b = pb.raw;
@@ -893,7 +877,7 @@ void LREngine::finish_layout(PrepBuf& pb, hipStream_t s, bool dp_hist) {
     ensure_tier(pb, nU, s);
     prep.near_end = kNumNumeric + n_near;
     TWTML_HIP_CHECK(hipMemsetAsync(prep.slot_hist + kNumNumeric, 0, sizeof(uint32_t) * size_t(nU), s));
-    if (dp_hist) launch_union_hist(pb.gathered, world_, pb.c1_maxu, prep, s);
+    if (dp_max_u >= 0) launch_union_hist(pb.gathered, world_, dp_max_u, prep, s);
     else launch_tier_hist(prep, nU, num_cu_, s);
     launch_tier_layout(prep, res.entries, nU, n_near, ns, nl, num_cu_, b, fp, lazy, s);
     pb.nl = nl;
@@ -905,7 +889,7 @@ void LREngine::finish_layout(PrepBuf& pb, hipStream_t s, bool dp_hist) {
     if (prep.hybrid) launch_remap_hybrid(prep, res.entries, ns, kNumNumeric + nU, num_cu_, b, fp, lazy, s);
     else launch_remap(prep, res.entries, nU, u16, s);
   }
-  if (lazy) raw_.release_slot(pb.slot, s);
+  if (lazy) raw_.release_slot(slot, s);
   prep.dedup = dedup ? 1 : 0;
   if (prep.dedup) launch_dedup(prep, ns, kNumNumeric + nU, res.n_kept, s);
   res.n_near = pb.n_near;
@@ -916,13 +900,13 @@ void LREngine::finish_layout(PrepBuf& pb, hipStream_t s, bool dp_hist) {
     TWTML_HIP_CHECK(hipMemcpyAsync(pb.host_counters + 3, prep.counters + 3, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     TWTML_HIP_CHECK(hipEventRecord(pb.ev_flag, s));
   }
-  pb.stage = 2;
 }
 
 // ---------------------------------------------------------------------------
 // train: GD on a prepared batch, on the compute stream (after its prep).
 // ---------------------------------------------------------------------------
-BatchResult LREngine::train(PrepBuf& pb, bool want_pred, int64_t plot_points) {
+BatchResult LREngine::train(int buf, bool want_pred, int64_t plot_points) {
+  PrepBuf& pb = pb_[buf];
   TWTML_HIP_CHECK(hipSetDevice(device_));
   hipStream_t s = compute_;
   const int world = world_;
@@ -1019,13 +1003,8 @@ BatchResult LREngine::train(PrepBuf& pb, bool want_pred, int64_t plot_points) {
           // the next batch's packets are ready on every rank: all-gather them
           // here, between iterations j + depth - 1 and j + depth -- every rank
           // sees the same all-reduced flag at the same point
-          PrepBuf* nb = nullptr;
-          {
-            std::lock_guard<std::mutex> lk(mu_);
-            for (auto& b : pb_)
-              if (&b != &pb && b.c1 == 1) nb = &b;
-          }
-          if (nb) issue_c1(*nb, v >> 2);
+          const PrepHandoff::Waiting nb = handoff_->packet_waiting(buf);
+          if (nb.buf >= 0) issue_c1(nb.buf, nb.nu_local, v >> 2);
         }
         if (v & 1) break;
       }
@@ -1210,62 +1189,54 @@ void LREngine::print_iter_timing(int iters) {
 // ---------------------------------------------------------------------------
 void LREngine::prep_worker() {
   (void)hipSetDevice(device_);
-  std::unique_lock<std::mutex> lk(mu_);
   for (;;) {
-    cv_.wait(lk, [&] { return stop_ || job_ >= 0; });
-    if (stop_) return;
-    PrepBuf& b = pb_[job_];
-    const int slot = b.slot;
-    const int64_t now_ms = b.now_ms;
-    lk.unlock();
+    const PrepHandoff::Job job = handoff_->next_job();
+    if (job.buf < 0) return;
+    PrepBuf& b = pb_[job.buf];
     std::exception_ptr err;
     try {
-      prepare_local(b, slot, now_ms, pstream_);
+      const int64_t nu_local = prepare_local(b, job.slot, job.now_ms, pstream_);
       if (dp_) {
         // packet ready: announce it (the ready word travels in the gradient
         // all-reduce) and wait for the training thread's all-gather
-        lk.lock();
-        b.c1 = 1;
-        __atomic_store_n(ready_host_.get(), b.nu_local + 1, __ATOMIC_RELEASE);
-        cv_.notify_all();
-        cv_.wait(lk, [&] { return stop_ || b.c1 == 2 || b.c1 == -2; });
-        if (stop_) return;
-        if (b.c1 == -2) throw std::runtime_error("DP: a peer rank failed to prepare this batch");
-        lk.unlock();
-        prepare_global_dp(b, pstream_);
+        const int64_t max_u = handoff_->packet_ready(job.buf, nu_local);
+        if (max_u < 0) return;   // shut down
+        prepare_global_dp(b, job.slot, max_u, pstream_);
       } else {
-        prepare_global(b, pstream_);
+        prepare_global(b, job.slot, pstream_);
       }
     } catch (...) {
       err = std::current_exception();
     }
-    if (!lk.owns_lock()) lk.lock();
-    b.error = err;
-    if (err && b.c1 == 1) b.c1 = -1;
-    b.state = 2;
-    job_ = -1;
-    cv_.notify_all();
+    handoff_->job_done(job.buf, err);
   }
 }
 
-// Caller holds mu_: start preparing the next submitted slot if a buffer and
-// the prep thread are free.
-void LREngine::schedule_ahead_locked() {
-  if (!overlap_ || job_ >= 0 || submitted_.empty()) return;
-  int free_buf = -1;
-  for (int k = 0; k < 2; ++k)
-    if (pb_[k].state == 0) free_buf = k;
-  if (free_buf < 0) return;
-  const auto next = submitted_.front();
-  for (auto& b : pb_)
-    if (b.state != 0 && b.slot == next.first) return;   // already there
-  submitted_.pop_front();
-  PrepBuf& b = pb_[free_buf];
-  b.state = 1;
-  b.slot = next.first;
-  b.now_ms = next.second;
-  job_ = free_buf;
-  cv_.notify_all();
+// The whole preparation on the training thread: a batch that was not prepared
+// ahead, or (one GPU) one prepared ahead under another batch time.  A failure
+// frees the buffer before it propagates.
+void LREngine::prepare_here(int buf, int slot, int64_t now_ms) {
+  PrepBuf& b = pb_[buf];
+  try {
+    int64_t nu_local = 0;
+    try {
+      nu_local = prepare_local(b, slot, now_ms, pstream_);
+    } catch (...) {
+      if (dp_) (void)issue_c1_inline(-1, 0);   // the peers raise too instead of waiting
+      throw;
+    }
+    if (dp_) {
+      const int64_t max_u = issue_c1_inline(buf, nu_local);
+      if (max_u < 0) throw std::runtime_error("DP: a peer rank failed to prepare this batch");
+      prepare_global_dp(b, slot, max_u, pstream_);
+    } else {
+      prepare_global(b, slot, pstream_);
+    }
+  } catch (...) {
+    handoff_->release(buf);
+    throw;
+  }
+  handoff_->prepared_here(buf);
 }
 
 // A submitted batch that will never be processed (the host pipeline matched
@@ -1276,21 +1247,8 @@ void LREngine::schedule_ahead_locked() {
 // every later batch, and a reused slot races its own stale preparation.
 void LREngine::discard(int slot) {
   TWTML_HIP_CHECK(hipSetDevice(device_));
-  std::unique_lock<std::mutex> lk(mu_);
-  if (dp_)   // every rank must issue the same collectives: no rank may skip a batch
-    throw std::logic_error("DP: every submitted batch must be processed, in submission order");
-  for (auto it = submitted_.begin(); it != submitted_.end();)
-    it = it->first == slot ? submitted_.erase(it) : std::next(it);
-  for (auto& b : pb_) {
-    if (b.state == 0 || b.slot != slot) continue;
-    cv_.wait(lk, [&] { return b.state == 2; });
-    b.state = 0;
-    b.c1 = 0;
-    b.error = nullptr;
-  }
-  raw_.release_slot(slot, pstream_);
-  schedule_ahead_locked();
-  lk.unlock();           // (the copy stream does not depend on the prep thread)
+  handoff_->discard(slot);
+  raw_.release_slot(slot, pstream_);   // behind the discarded preparation's reads, if there was one
   raw_.wait_h2d(slot);   // the host staging buffer of the slot may be rewritten on return
 }
 
@@ -1298,136 +1256,30 @@ BatchResult LREngine::process(int slot, int64_t now_ms, bool want_pred, int64_t 
   TraceRange tr_batch("twtml.lr.batch");
   TWTML_HIP_CHECK(hipSetDevice(device_));
   const auto t_in = std::chrono::steady_clock::now();
-  int k = -1;
-  bool ahead = false;
-  {
-    std::unique_lock<std::mutex> lk(mu_);
-    for (int i = 0; i < 2; ++i)
-      if (pb_[i].state != 0 && pb_[i].slot == slot) k = i;
-    ahead = k >= 0;
-    if (k >= 0 && dp_) {
-      // DP: the packets were all-gathered during the previous batch, or are
-      // now, in line -- the same choice on every rank (it follows the
-      // all-reduced ready words); then the prep thread finishes the layout
-      cv_.wait(lk, [&] { return pb_[k].c1 != 0 || pb_[k].state == 2; });
-      if (pb_[k].c1 == 1) {
-        lk.unlock();
-        const bool ok = issue_c1_inline(&pb_[k]);
-        lk.lock();
-        if (!ok) {   // a peer's prep failed: release the prep thread, raise on every rank
-          pb_[k].c1 = -2;
-          cv_.notify_all();
-        }
-      } else if (pb_[k].c1 == 0 && pb_[k].state == 2 && pb_[k].error) {
-        // this rank's local prep failed before its packet: tell the peers
-        lk.unlock();
-        (void)issue_c1_inline(nullptr);
-        lk.lock();
-      }
-      cv_.wait(lk, [&] { return pb_[k].state == 2; });
-      if (pb_[k].error) {
-        std::exception_ptr err = pb_[k].error;
-        pb_[k].error = nullptr;
-        pb_[k].state = 0;
-        pb_[k].c1 = 0;
-        std::rethrow_exception(err);
-      }
-    } else if (k >= 0) {
-      cv_.wait(lk, [&] { return pb_[k].state == 2; });
-      // prepared ahead with the batch time given at submit; a different time
-      // here is re-prepared
-      if (pb_[k].error || pb_[k].now_ms != now_ms) {   // failed ahead / other time
-        std::exception_ptr err = pb_[k].error;
-        pb_[k].error = nullptr;
-        if (err && pb_[k].now_ms == now_ms) {
-          pb_[k].state = 0;
-          std::rethrow_exception(err);
-        }
-        pb_[k].state = 1;
-        lk.unlock();
-        prepare_local(pb_[k], slot, now_ms, pstream_);
-        prepare_global(pb_[k], pstream_);
-        lk.lock();
-        pb_[k].state = 2;
-      }
-    } else {
-      // not prepared ahead: drop it from the submission queue, prepare in line
-      for (auto it = submitted_.begin(); it != submitted_.end(); ++it)
-        if (it->first == slot) { submitted_.erase(it); break; }
-      if (dp_) {
-        // every rank must issue the same collectives in the same order: a
-        // batch prepared (and possibly all-gathered) ahead may not be skipped
-        for (int i = 0; i < 2; ++i)
-          if (pb_[i].state != 0)
-            throw std::logic_error("DP: batches must be processed in submission order");
-      }
-      for (int i = 0; i < (overlap_ ? 2 : 1); ++i)
-        if (pb_[i].state == 0) k = i;
-      if (k < 0) {
-        // one GPU: every buffer holds a batch prepared ahead that is not this
-        // one (submitted but processed out of order): evict one -- its slot
-        // goes back to the front of the queue and is prepared again when due
-        cv_.wait(lk, [&] { return job_ < 0; });
-        for (int i = 0; i < 2 && k < 0; ++i)
-          if (pb_[i].state == 2) {
-            submitted_.push_front({pb_[i].slot, pb_[i].now_ms});
-            pb_[i].state = 0;
-            pb_[i].error = nullptr;
-            k = i;
-          }
-        if (k < 0) throw std::logic_error("no free prepared-batch buffer");
-      }
-      pb_[k].state = 1;
-      pb_[k].slot = slot;
-      pb_[k].now_ms = now_ms;
-      lk.unlock();
-      try {
-        bool local_ok = false;
-        try {
-          prepare_local(pb_[k], slot, now_ms, pstream_);
-          local_ok = true;
-        } catch (...) {
-          if (dp_) (void)issue_c1_inline(nullptr);   // the peers raise too instead of waiting
-          throw;
-        }
-        if (dp_) {
-          if (local_ok && !issue_c1_inline(&pb_[k]))
-            throw std::runtime_error("DP: a peer rank failed to prepare this batch");
-          prepare_global_dp(pb_[k], pstream_);
-        } else {
-          prepare_global(pb_[k], pstream_);
-        }
-      } catch (...) {
-        lk.lock();
-        pb_[k].state = 0;
-        pb_[k].c1 = 0;
-        throw;
-      }
-      lk.lock();
-      pb_[k].state = 2;
+  using Action = PrepHandoff::Action;
+  PrepHandoff::Claim c = handoff_->claim(slot, now_ms);
+  for (; c.action != Action::Train && c.action != Action::PrepareHere; c = handoff_->claim(slot, now_ms)) {
+    // DP, the batch's packets were not all-gathered during the previous batch
+    if (c.action == Action::ReportLocalFailure) {
+      (void)issue_c1_inline(-1, 0);   // this rank's local prep failed before its packet: tell the peers
+    } else if (issue_c1_inline(c.buf, c.nu_local) < 0) {
+      handoff_->peer_failed(c.buf);   // a peer's prep failed: release the prep thread, raise on every rank
     }
-    last_buf_ = k;
-    schedule_ahead_locked();   // batch t+1's prep overlaps batch t's training
   }
+  if (c.action == Action::PrepareHere) prepare_here(c.buf, slot, now_ms);
+  last_buf_ = c.buf;
   BatchResult res;
   const auto t_train = std::chrono::steady_clock::now();
   try {
-    res = train(pb_[k], want_pred, plot_points);
-    res.prepared_ahead = ahead;
+    res = train(c.buf, want_pred, plot_points);
+    res.prepared_ahead = c.ahead;
     res.wait_ms = std::chrono::duration<float, std::milli>(t_train - t_in).count();
     res.train_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_train).count();
   } catch (...) {
-    std::lock_guard<std::mutex> lk(mu_);
-    pb_[k].state = 0;
-    pb_[k].c1 = 0;
+    handoff_->release(c.buf);
     throw;
   }
-  {
-    std::lock_guard<std::mutex> lk(mu_);
-    pb_[k].state = 0;
-    pb_[k].c1 = 0;
-    schedule_ahead_locked();
-  }
+  handoff_->trained(c.buf);   // batch t+2's prep may start
   return res;
 }
 

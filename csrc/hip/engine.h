@@ -1,7 +1,8 @@
 // MI355X micro-batch engine for StreamingLinearRegressionWithSGD.
 //
 // One engine per process/GPU.  A micro-batch flows:
-//   pinned host RawBatch --(copy stream, async H2D)--> device slot (x4)
+//   pinned host RawBatch --(copy stream, async H2D)--> one of the device raw
+//   slots (LRConfig::raw_slots, kDefaultRawSlots by default)
 //   prep stream: decode / lower rows -> filter -> length sort -> featurize
 //   -> compact -> layout (hybrid / tiered) -- for batch t+1 while batch t
 //   trains (prep thread).  DP: the local part ends in one packet per rank
@@ -11,7 +12,7 @@
 //   compute stream: gather w -> numIterations x ( fused predict/gradient
 //   kernel -> [RCCL all-reduce of the packed gradient] -> fp64 update +
 //   convergence ) -> scatter w
-// Four device slots let the H2D of the next batches overlap batch t's
+// Several raw slots let the H2D of the next batches overlap batch t's
 // training (SURVEY §2.4 "Ingest || compute pipelining").  Output op #1 (prequential stats)
 // is fused into iteration 1, so it sees the weights before training on the
 // batch (LinearRegression.scala:53-86 ordering).
@@ -19,9 +20,6 @@
 #include <cmath>
 #include <hip/hip_runtime.h>
 
-#include <condition_variable>
-#include <deque>
-#include <exception>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -33,6 +31,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "owned.h"
+#include "prep_handoff.h"
 #include "raw_slots.h"
 
 namespace twtml {
@@ -191,7 +190,8 @@ struct EvalResult {
 // (by the engine's prep thread) while batch t trains on the compute stream.
 // A buffer's device memory (its arena) is touched by the prep thread
 // (ensure_tier, the packet) and by the training thread (issue_c1), never by
-// both at once: the c1 / state protocol under LREngine::mu_ hands it over.
+// both at once: PrepHandoff (prep_handoff.h) hands it over, and keeps the
+// buffer's state, raw slot, batch time and packet sizes.
 struct PrepBuf {
   DevArena arena;                     // owns every device buffer below (dp's included)
   DevPrepared dp{};
@@ -208,22 +208,12 @@ struct PrepBuf {
   Pinned<int64_t> host_hdr;           // pinned [world * kC1HeaderWords / 2] gathered headers
   Pinned<double> host_bounds;         // pinned [kBoundsLen]
   Event ev_c1;                        // compute stream, after the all-gather
-  int64_t nu_local = 0;               // this rank's active ids (packet pairs)
-  int64_t c1_maxu = 0;                // pairs per rank in the all-gather
-  int c1 = 0;                         // guarded by mu_: 0 -, 1 packet ready, 2 all-gather issued, -1 failed,
-                                      // -2 a peer failed (no all-gather)
   Pinned<int64_t> host_norm;          // pinned [2] rows lowered / narrowed on the device
   double* bounds = nullptr;           // device [kBoundsLen] batch bounds of the fixed-point scales
                                       // (DP: the max over ranks)
   Event ev_start, ev_done;
   Event ev_flag;                      // prep stream, after the copy of the far-CSC position flag (tiered)
-  // guarded by LREngine::mu_
-  int state = 0;                      // 0 free, 1 being prepared, 2 prepared
-  int slot = -1;
-  int64_t now_ms = 0;
-  std::exception_ptr error;
   // prepare() outputs
-  int stage = 0;                      // 1: local part done (prepare_local), 2: ready to train
   DevRawBatch raw{};                  // the raw slot's device view (global part, lazy remap)
   FeaturizeParams fp{};
   bool lazy = false;
@@ -355,26 +345,48 @@ class LREngine {
   void alloc_prepared(PrepBuf& b);
   void ensure_score();
   void ensure_eval();
-  bool training_owns_locked(int slot) const;
+  FeaturizeParams featurize_params(int64_t now_ms, bool apply_filter) const;
+  // TWTML_INJECT_*_FAIL=<rank>:<n> (tests): throws on this rank's n-th call
+  void inject_failure(const char* env, int& calls, const char* what);
+  // What score() and evaluate() share: the ownership check, the raw slot,
+  // the start event (eval: evaluate()'s buffers and events) and filter ..
+  // launch_score with the caller's link.  False if the slot holds no rows.
+  struct ScorePass {
+    int64_t n_raw = 0;
+    DevRawBatch b{};
+    double* pred = nullptr;    // device [n] predictions
+    int64_t* rows = nullptr;   // device [n] scored raw row ids (null: every row)
+  };
+  bool score_pass(const char* who, int slot, int64_t now_ms, bool apply_filter, int link, double link_thr,
+                  bool eval, ScorePass& p);
   void ensure_compact(int64_t ns);
   void ensure_part(int64_t n);
   int64_t active_set_hint() const;
   void ensure_tier(PrepBuf& b, int64_t n_unique, hipStream_t s);
-  void prepare_local(PrepBuf& b, int slot, int64_t now_ms, hipStream_t s);
-  void prepare_global(PrepBuf& b, hipStream_t s);
-  // DP: the all-gather of b's packet, on the compute stream (max_u pairs per rank)
-  void issue_c1(PrepBuf& b, int64_t max_u);
+  // The batch's raw slot, its packet's pairs (nu_local) and the all-gather's
+  // pairs per rank (max_u) are kept by handoff_, not in the buffer: they are
+  // passed in.  prepare_local returns nu_local (DP; else 0).
+  int64_t prepare_local(PrepBuf& b, int slot, int64_t now_ms, hipStream_t s);
+  void prepare_global(PrepBuf& b, int slot, hipStream_t s);
+  // all of a batch's preparation on the calling (training) thread
+  void prepare_here(int buf, int slot, int64_t now_ms);
+  // DP: the all-gather of pb_[buf]'s packet (nu_local pairs), on the compute
+  // stream, max_u pairs per rank
+  void issue_c1(int buf, int64_t nu_local, int64_t max_u);
   // DP, not issued during the previous batch: size it with an all-reduce
-  // first, which also carries every rank's prep status (b == null: this
-  // rank's prep failed).  False (no all-gather issued) if any rank failed.
-  bool issue_c1_inline(PrepBuf* b);
+  // first, which also carries every rank's prep status (buf < 0: this
+  // rank's prep failed).  Returns max_u, or -1 (no all-gather issued) if any
+  // rank failed.
+  int64_t issue_c1_inline(int buf, int64_t nu_local);
   // DP: union, global counts / bounds and layout from the gathered packets
-  void prepare_global_dp(PrepBuf& b, hipStream_t s);
+  void prepare_global_dp(PrepBuf& b, int slot, int64_t max_u, hipStream_t s);
   // shared tail of prepare_global / prepare_global_dp: compact space + layout
-  void finish_layout(PrepBuf& b, hipStream_t s, bool dp_hist);
-  BatchResult train(PrepBuf& b, bool want_pred, int64_t plot_points);
+  // dp_max_u >= 0: the tiered near tier's slot counts come from the gathered
+  // packets (every rank numbers the slots from the same counts), else they
+  // are sampled here
+  void finish_layout(PrepBuf& b, int slot, hipStream_t s, int64_t dp_max_u);
+  BatchResult train(int buf, bool want_pred, int64_t plot_points);
   void prep_worker();
-  void schedule_ahead_locked();
   void print_iter_timing(int iters);
   double wait_flag(int j);
 
@@ -397,12 +409,9 @@ class LREngine {
   Pinned<int64_t> ready_host_;      // DP: pinned mapped ready word (next packet's pairs + 1; 0: none)
   int64_t* dnu_ = nullptr;          // DP: device [world] active-set sizes (in-line all-gather sizing)
   Pinned<int64_t> hnu_;             // pinned [world]
-  // prepare-ahead: submitted slots in order, the prep thread's job (a pb_ index)
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::deque<std::pair<int, int64_t>> submitted_;
-  int job_ = -1;
-  bool stop_ = false;
+  // prepare-ahead: who holds which pb_ and what happens to it next (built by
+  // the constructor once overlap_, dp_ and ready_host_ are known)
+  std::unique_ptr<PrepHandoff> handoff_;
   std::thread worker_;
   DevSgd sgd_{};
   int64_t ns_cap_ = 0;

@@ -413,6 +413,41 @@ def test_utf8_truncated_sequences_stay_in_their_row(hip_module):
         np.testing.assert_array_equal(rows[k], np.sort(want), err_msg=f"row {k}")
 
 
+def test_prepared_ahead_batch_processed_under_another_time(hip_module):
+    """A batch prepared ahead with the time it was submitted with, then
+    processed under another one, is prepared again with that time: stats,
+    loss history, iterations and weights equal, bit for bit, those of an engine
+    that prepares both batches in line (the GD is exact integer arithmetic,
+    independent of layout and buffer) -- and differ from the submitted time's."""
+    F, day = 1000, 86_400_000
+    cfg = SynthConfig.profile("twitter", seed=29)
+    raws = [generate_batch(cfg, t * 600, 600, batch_time_ms=NOW + t * 5000) for t in range(2)]
+    times = [raws[0].batch_time_ms, raws[1].batch_time_ms + day]
+    for raw in raws:
+        assert featurize_batch(raw, F, 100, 1000).n >= 16   # one chunk of kept rows at least
+
+    def run(overlap, t1):
+        eng = _engine(F, max_rows=1024, max_units=1024 * 300, num_iterations=5, overlap=overlap)
+        for slot, raw in enumerate(raws):
+            eng.submit(eng.staging(slot).load(raw), slot)   # queued with raw.batch_time_ms
+        out = [eng.process(0, times[0]), eng.process(1, t1)]
+        return out, eng.get_weights()
+
+    (a0, a1), wa = run(True, times[1])
+    (b0, b1), wb = run(False, times[1])
+    assert a1["prepared_ahead"] and not a0["prepared_ahead"] and not b1["prepared_ahead"]
+    for ra, rb in ((a0, b0), (a1, b1)):
+        assert ra["n_kept"] == rb["n_kept"] >= 16
+        assert list(ra["stats"]) == list(rb["stats"])
+        assert list(ra["loss_history"]) == list(rb["loss_history"])
+        assert ra["iterations"] == rb["iterations"] > 0
+    np.testing.assert_array_equal(wa.view(np.int64), wb.view(np.int64))
+    # the time given to process() was the one used
+    (_, c1), wc = run(True, raws[1].batch_time_ms)
+    assert c1["prepared_ahead"] and c1["n_kept"] == a1["n_kept"]
+    assert np.any(wa != wc)
+
+
 def test_long_run_parity_wide(hip_module):
     """the fixed-point GD departs from MLlib's fp64 update
     (weights quantised relative to max |w|, residuals to a bound); over a

@@ -334,6 +334,34 @@ def test_non_interference_tiered(hip_module):
     assert r.returncode == 0 and "scenario ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
+def test_slot_owned_by_training_is_refused(hip_module):
+    """A raw slot that holds a batch queued for training takes no score-only
+    batch and is neither scored nor evaluated; the refusals leave the queued
+    batch as it was: it trains to the bits of an engine that never saw them."""
+    F = 1000
+    synth = SynthConfig.profile("twitter", seed=3)
+    A, X = (generate_batch(synth, t * 64, 64, batch_time_ms=NOW + t) for t in range(2))
+    kw = dict(max_rows=1024, max_units=1024 * 300, num_iterations=5)
+    direct = _engine(F, **kw)
+    want = direct.train_batch(A, want_pred=False)
+    assert want["n_kept"] == featurize_batch_native(A, F, 100, 1000, now_ms=A.batch_time_ms).n > 0
+    eng = _engine(F, **kw)
+    assert eng.prefetch(A)   # queued: submitted, not processed yet
+    (_, slot), = eng._pipe._inflight.values()
+    hb = eng.staging((slot + 1) % eng.raw_slots).load(X)
+    owned = "queued or prepared for training"
+    with pytest.raises(RuntimeError, match=owned):
+        eng._eng.submit(hb._hb, int(hb.n), int(hb.bytes), int(slot), int(hb.ext_text), int(hb.batch_time_ms), False)
+    with pytest.raises(RuntimeError, match=owned):
+        eng._eng.score(int(slot), int(A.batch_time_ms), False, 0)
+    with pytest.raises(RuntimeError, match=owned):
+        eng._eng.evaluate(int(slot), int(A.batch_time_ms), False)
+    got = eng.train_batch(A, want_pred=False)
+    assert eng._pipe.hits == 1 and got["n_kept"] == want["n_kept"]
+    assert list(got["stats"]) == list(want["stats"]) and got["iterations"] == want["iterations"]
+    np.testing.assert_array_equal(eng.get_weights().view(np.int64), direct.get_weights().view(np.int64))
+
+
 def test_dp_loopback_scoring_issues_no_collective(hip_module):
     """Two DP replicas (loopback communicator), each scoring a different shard
     between two trained batches: they stay bit-identical, equal the run
