@@ -7,6 +7,7 @@
 #include <pybind11/stl.h>
 
 #include <memory>
+#include <optional>
 
 #include "alloc.h"
 #include "comm.h"
@@ -40,6 +41,31 @@ static LRConfig lr_config(const py::dict& d) {
   GET(loss, int32_t) GET(label_threshold, int64_t) GET(threshold, double)
 #undef GET
   return c;
+}
+
+// A selection's result as arrays owned by the caller (the engine's pinned
+// block is reused): rows, values (the original bits), payload, the counts.
+py::dict twtml::top_dict(const TopResult& r) {
+  const py::ssize_t m = py::ssize_t(r.n_top);
+  py::array_t<int64_t> rows(m);
+  py::array_t<double> values(m);
+  py::array_t<int32_t> payload(m);
+  if (m > 0) {
+    std::memcpy(rows.mutable_data(), r.rows, sizeof(int64_t) * size_t(m));
+    std::memcpy(values.mutable_data(), r.bits, sizeof(double) * size_t(m));
+    for (py::ssize_t i = 0; i < m; ++i) payload.mutable_data()[i] = int32_t(r.payload[i]);
+  }
+  py::dict d;
+  d["n_raw"] = r.n_raw;
+  d["n_scored"] = r.n_scored;
+  d["n_top"] = r.n_top;
+  d["n_nan"] = r.n_nan;
+  d["rows"] = rows;
+  d["values"] = values;
+  d["payload"] = payload;
+  d["top_ms"] = r.top_ms;
+  d["wall_ms"] = r.wall_ms;
+  return d;
 }
 
 static py::dict result_dict(BatchResult& r) {
@@ -401,6 +427,41 @@ PYBIND11_MODULE(_twtml_hip, m) {
            "held-out evaluation of the batch in `slot` (submitted with train=False) under the current weights: "
            "iw = the int64 accumulator words (n, n_nan, tn, fp, fn, tp, -, scored rows, hist[2][4097]), "
            "dw = the fp64 sums (kernels.h launch_eval)")
+      .def("top",
+           [](LREngine& e, int slot, int64_t now_ms, bool apply_filter, int n, bool largest) {
+             TopResult r;
+             {
+               py::gil_scoped_release nogil;
+               r = e.top(slot, now_ms, apply_filter, n, largest);
+             }
+             return top_dict(r);
+           },
+           py::arg("slot"), py::arg("now_ms"), py::arg("apply_filter"), py::arg("n"), py::arg("largest") = true,
+           "the n best rows of the batch in `slot` (submitted with train=False) by margin, selected on the "
+           "device: rows / values in the result's order (best first, ties by ascending row), n_top, n_nan")
+      .def("debug_top_select",
+           [](LREngine& e, py::array_t<double, py::array::c_style | py::array::forcecast> values,
+              std::optional<py::array_t<int64_t, py::array::c_style | py::array::forcecast>> rows, int n,
+              bool largest) {
+             if (values.ndim() != 1 || (rows && (rows->ndim() != 1 || rows->size() != values.size())))
+               throw std::invalid_argument("debug_top_select(): values and rows are 1-d arrays of one length");
+             TopResult r;
+             {
+               const double* v = values.data();
+               const int64_t* rp = rows ? rows->data() : nullptr;
+               const int64_t count = values.size();
+               py::gil_scoped_release nogil;
+               r = e.debug_top_select(v, count, rp, n, largest);
+             }
+             py::dict d = top_dict(r);
+             d["max_grid"] = kTopMaxGrid;
+             d["block"] = kBlock;
+             d["digit_bits"] = py::make_tuple(11, 11, 11, 11, 11, 9);   // of the value key, most significant first
+             return d;
+           },
+           py::arg("values"), py::arg("rows") = py::none(), py::arg("n") = 1, py::arg("largest") = true,
+           "debug/test: the selection kernels alone over host values (at most max_rows); also the grid and "
+           "block constants of a select pass")
       .def("process",
            [](LREngine& e, int slot, int64_t now_ms, bool want_pred, int64_t plot_points) {
              BatchResult r;

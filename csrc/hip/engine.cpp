@@ -552,19 +552,20 @@ void LREngine::ensure_score() {
 // The pass score() and evaluate() share (engine.h ScorePass); the caller
 // records its end event, releases the raw slot and copies its results.
 bool LREngine::score_pass(const char* who, int slot, int64_t now_ms, bool apply_filter, int link, double link_thr,
-                          bool eval, ScorePass& p) {
+                          ScoreKind kind, ScorePass& p) {
   if (handoff_->owns(slot))
     throw std::logic_error(std::string(who) + ": the slot holds a batch queued or prepared for training");
   p.n_raw = raw_.rows(slot);
   if (p.n_raw == 0) return false;
-  if (eval) ensure_eval();
+  if (kind == kPassEval) ensure_eval();
+  else if (kind == kPassTop) ensure_top();
   else ensure_score();
   hipStream_t s = compute_;
   p.b = raw_.acquire(slot, s);
   const FeaturizeParams fp = featurize_params(now_ms, apply_filter);
   p.pred = reinterpret_cast<double*>(score_out_ + 8);
   p.rows = apply_filter ? score_out_ + 8 + p.b.n : nullptr;
-  TWTML_HIP_CHECK(hipEventRecord(eval ? eval_ev_[0] : score_ev_[0], s));
+  TWTML_HIP_CHECK(hipEventRecord(kind == kPassEval ? eval_ev_[0] : (kind == kPassTop ? top_ev_[0] : score_ev_[0]), s));
   launch_score_init(score_dp_, s);
   launch_filter_sort(p.b, score_dp_, fp, s);
   launch_chunk_layout(p.b, score_dp_, s);
@@ -585,7 +586,7 @@ ScoreResult LREngine::score(int slot, int64_t now_ms, bool apply_filter, int lin
   const auto t_in = std::chrono::steady_clock::now();
   ScoreResult res;
   ScorePass p;
-  const bool any = score_pass("score()", slot, now_ms, apply_filter, link, logit_threshold(), false, p);
+  const bool any = score_pass("score()", slot, now_ms, apply_filter, link, logit_threshold(), kPassScore, p);
   res.n_raw = p.n_raw;
   if (!any) return res;
   hipStream_t s = compute_;
@@ -626,7 +627,7 @@ EvalResult LREngine::evaluate(int slot, int64_t now_ms, bool apply_filter) {
   EvalResult res;
   res.binary = cfg_.loss == kLossLogistic;
   ScorePass p;
-  const bool any = score_pass("evaluate()", slot, now_ms, apply_filter, kLinkMargin, 0.0, true, p);
+  const bool any = score_pass("evaluate()", slot, now_ms, apply_filter, kLinkMargin, 0.0, kPassEval, p);
   res.n_raw = p.n_raw;
   if (!any) return res;
   hipStream_t s = compute_;
@@ -647,6 +648,89 @@ EvalResult LREngine::evaluate(int slot, int64_t now_ms, bool apply_filter) {
   res.dw = reinterpret_cast<const double*>(h + kEvalIntWords);
   TWTML_HIP_CHECK(hipEventElapsedTime(&res.eval_ms, eval_ev_[0], eval_ev_[1]));
   res.wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+  return res;
+}
+
+// ---------------------------------------------------------------------------
+// Top-N (topn.hip): score()'s pass, then the selection over the margins.
+// ---------------------------------------------------------------------------
+void LREngine::ensure_top() {
+  ensure_score();
+  if (top_sc_.out) return;
+  top_host_.alloc(sizeof(int64_t) * top_out_words(kTopNMax), hipHostMallocDefault);
+  top_ev_[0] = Event(hipEventDefault);
+  top_ev_[1] = Event(hipEventDefault);
+  top_sc_ = top_scratch_carve(score_arena_.alloc<int64_t>(top_scratch_words()));
+}
+
+// the result block of a selection of n, copied to the pinned buffer (syncs the compute stream)
+TopResult LREngine::top_result(int n) {
+  hipStream_t s = compute_;
+  TWTML_HIP_CHECK(hipMemcpyAsync(top_host_.get(), top_sc_.out, sizeof(int64_t) * top_out_words(n),
+                                 hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipStreamSynchronize(s));
+  const int64_t* h = top_host_.get();
+  TopResult res;
+  res.n_scored = h[kTopCnt];
+  res.n_top = h[kTopNTop];
+  res.n_nan = h[kTopNNan];
+  if (res.n_top < 0 || res.n_top > n || res.n_nan < 0 || res.n_top + res.n_nan > res.n_scored)
+    throw std::runtime_error("top(): the result block's counts are out of range");
+  res.bits = h + kTopHead;
+  res.rows = h + kTopHead + n;
+  res.payload = h + kTopHead + 2 * size_t(n);
+  return res;
+}
+
+static void check_top_n(int n) {
+  if (n < 1 || n > kTopNMax)
+    throw std::invalid_argument("top(): n must be in [1, " + std::to_string(kTopNMax) + "]; use score() for every row");
+}
+
+TopResult LREngine::top(int slot, int64_t now_ms, bool apply_filter, int n, bool largest) {
+  check_top_n(n);
+  TraceRange tr("twtml.lr.top");
+  TWTML_HIP_CHECK(hipSetDevice(device_));
+  const auto t_in = std::chrono::steady_clock::now();
+  ScorePass p;
+  if (!score_pass("top()", slot, now_ms, apply_filter, kLinkMargin, 0.0, kPassTop, p)) {
+    TopResult res;
+    res.n_raw = p.n_raw;
+    return res;
+  }
+  hipStream_t s = compute_;
+  launch_top_select(p.pred, p.rows, nullptr, score_dp_.counters, p.b.n, n, largest, top_sc_, s);
+  TWTML_HIP_CHECK(hipEventRecord(top_ev_[1], s));
+  raw_.release_slot(slot, s);   // the raw slot may be overwritten now
+  TopResult res = top_result(n);
+  res.n_raw = p.n_raw;
+  check_scored("top()", res.n_scored, p.b.n, apply_filter);
+  TWTML_HIP_CHECK(hipEventElapsedTime(&res.top_ms, top_ev_[0], top_ev_[1]));
+  res.wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+  return res;
+}
+
+TopResult LREngine::debug_top_select(const double* values, int64_t count, const int64_t* rows, int n, bool largest) {
+  check_top_n(n);
+  if (count < 0 || count > cfg_.max_rows) throw std::invalid_argument("debug_top_select(): more values than max_rows");
+  TWTML_HIP_CHECK(hipSetDevice(device_));
+  ensure_top();
+  hipStream_t s = compute_;
+  // the layout of a scoring pass: counters | values | rows
+  double* dv = reinterpret_cast<double*>(score_out_ + 8);
+  int64_t* dr = rows ? score_out_ + 8 + count : nullptr;
+  TWTML_HIP_CHECK(hipMemcpyAsync(score_out_, &count, sizeof(int64_t), hipMemcpyHostToDevice, s));
+  if (count > 0) {
+    TWTML_HIP_CHECK(hipMemcpyAsync(dv, values, sizeof(double) * size_t(count), hipMemcpyHostToDevice, s));
+    if (rows) TWTML_HIP_CHECK(hipMemcpyAsync(dr, rows, sizeof(int64_t) * size_t(count), hipMemcpyHostToDevice, s));
+  }
+  TWTML_HIP_CHECK(hipStreamSynchronize(s));   // the host arrays may go
+  TWTML_HIP_CHECK(hipEventRecord(top_ev_[0], s));
+  launch_top_select(dv, dr, nullptr, score_out_, count, n, largest, top_sc_, s);
+  TWTML_HIP_CHECK(hipEventRecord(top_ev_[1], s));
+  TopResult res = top_result(n);
+  res.n_raw = count;
+  TWTML_HIP_CHECK(hipEventElapsedTime(&res.top_ms, top_ev_[0], top_ev_[1]));
   return res;
 }
 

@@ -33,6 +33,7 @@
 #include "owned.h"
 #include "prep_handoff.h"
 #include "raw_slots.h"
+#include "topn.h"
 
 namespace twtml {
 
@@ -185,6 +186,19 @@ struct EvalResult {
   float wall_ms = 0.f;             // evaluate() on the host, end to end
 };
 
+// top(): the n best scored rows of one raw batch (topn.h).  The arrays point
+// into the engine's pinned result block and stay valid until the next top()
+// or debug_top_select() call.
+struct TopResult {
+  int64_t n_raw = 0, n_scored = 0;
+  int64_t n_top = 0, n_nan = 0;       // entries selected = min(n, n_scored - n_nan); NaN values, never selected
+  const int64_t* bits = nullptr;      // [n_top] value bits, best first (ties: ascending raw row id)
+  const int64_t* rows = nullptr;      // [n_top] raw row ids
+  const int64_t* payload = nullptr;   // [n_top] the payload column (0 without one)
+  float top_ms = 0.f;                 // device time, filter .. the selection's sort (events)
+  float wall_ms = 0.f;                // top() on the host, end to end
+};
+
 // One prepared micro-batch: filtered, featurized, compacted and laid out for
 // the GD kernels.  Two of them, so batch t+1 is prepared on the prep stream
 // (by the engine's prep thread) while batch t trains on the compute stream.
@@ -277,6 +291,21 @@ class LREngine {
   // and guarantees as score(): nothing of the model but the weights is read,
   // no collective is issued, same thread as process().
   EvalResult evaluate(int slot, int64_t now_ms, bool apply_filter);
+  // The n best rows of the batch in `slot` (1 <= n <= kTopNMax): score()'s
+  // pass with kLinkMargin, then the selection of topn.hip over the margins on
+  // the device -- largest: the highest margins first, else the lowest; equal
+  // margins by ascending raw row id; NaN margins never.  The margin is
+  // monotone in the probability and still separates rows whose probability
+  // has saturated to the same double, so the logistic engine selects on it
+  // too.  Only the result block (4 + 3 n words) crosses to the host.  Same
+  // preconditions and guarantees as score(): nothing of the model but the
+  // weights is read, no prepared buffer, training state or snapshot is
+  // touched, no collective is issued, same thread as process().  Scratch is
+  // allocated by the first call.
+  TopResult top(int slot, int64_t now_ms, bool apply_filter, int n, bool largest);
+  // Debug/test: the selection kernels alone over `count` (<= max_rows) host
+  // values (rows: their row ids, or null), copied to the scoring buffers.
+  TopResult debug_top_select(const double* values, int64_t count, const int64_t* rows, int n, bool largest);
   // Forget a submitted batch that will not be processed (one GPU only): the
   // slot may be submitted again afterwards (ops/ingest.py SlotPipeline).
   void discard(int slot);
@@ -345,12 +374,15 @@ class LREngine {
   void alloc_prepared(PrepBuf& b);
   void ensure_score();
   void ensure_eval();
+  void ensure_top();
+  TopResult top_result(int n);
   FeaturizeParams featurize_params(int64_t now_ms, bool apply_filter) const;
   // TWTML_INJECT_*_FAIL=<rank>:<n> (tests): throws on this rank's n-th call
   void inject_failure(const char* env, int& calls, const char* what);
-  // What score() and evaluate() share: the ownership check, the raw slot,
-  // the start event (eval: evaluate()'s buffers and events) and filter ..
+  // What score(), evaluate() and top() share: the ownership check, the raw
+  // slot, the start event (kind: whose buffers and events) and filter ..
   // launch_score with the caller's link.  False if the slot holds no rows.
+  enum ScoreKind { kPassScore, kPassEval, kPassTop };
   struct ScorePass {
     int64_t n_raw = 0;
     DevRawBatch b{};
@@ -358,7 +390,7 @@ class LREngine {
     int64_t* rows = nullptr;   // device [n] scored raw row ids (null: every row)
   };
   bool score_pass(const char* who, int slot, int64_t now_ms, bool apply_filter, int link, double link_thr,
-                  bool eval, ScorePass& p);
+                  ScoreKind kind, ScorePass& p);
   void ensure_compact(int64_t ns);
   void ensure_part(int64_t n);
   int64_t active_set_hint() const;
@@ -460,6 +492,11 @@ class LREngine {
   double* eval_part_ = nullptr;       // device [kEvalMaxGrid][kEvalF64Words]
   Pinned<int64_t> eval_host_;
   Event eval_ev_[2];
+  // top(): the selection scratch and result block (topn.h), from
+  // score_arena_, and the block's pinned host copy; allocated by the first top()
+  TopScratch top_sc_{};
+  Pinned<int64_t> top_host_;
+  Event top_ev_[2];
   // weight snapshot (snapshot.hip); allocated on the first snapshot_begin
   std::mutex snap_mu_;
   bool snap_pending_ = false;

@@ -161,16 +161,16 @@ void KMEngine::ensure_score() {
                     hipHostMallocDefault);
 }
 
-KMScoreResult KMEngine::score(int slot, bool apply_filter, int scaler_mode, const double* std) {
+int64_t KMEngine::score_kernels(const char* who, int slot, bool apply_filter, int scaler_mode, const double* std,
+                                KMScoreResult& res, double** cost_out) {
+  const std::string w(who);
   if (scaler_mode < kKmScalerBatch || scaler_mode > kKmScalerNone)
-    throw std::invalid_argument("score(): unknown scaler mode");
-  if (scaler_mode == kKmScalerGiven && !std) throw std::invalid_argument("score(): the given scaler needs std");
-  TraceRange tr("twtml.km.score");
+    throw std::invalid_argument(w + ": unknown scaler mode");
+  if (scaler_mode == kKmScalerGiven && !std) throw std::invalid_argument(w + ": the given scaler needs std");
   TWTML_HIP_CHECK(hipSetDevice(device_));
   hipStream_t s = compute_;
   const int k = cfg_.k, d = d_;
   ensure_score();
-  KMScoreResult res;
   res.sizes.assign(size_t(k), 0);
   const DevRawBatch b = raw_.acquire(slot, s);
   res.n_raw = b.n;
@@ -190,13 +190,13 @@ KMScoreResult KMEngine::score(int slot, bool apply_filter, int scaler_mode, cons
   int64_t n;
   std::memcpy(&n, host_out_ + 1, sizeof(int64_t));
   if (n < 0 || n > b.n || n > cfg_.max_rows || (!apply_filter && n != b.n))
-    throw std::runtime_error("score(): kept-row count out of range");
+    throw std::runtime_error(w + ": kept-row count out of range");
   res.n_scored = n;
   if (n == 0) {   // nothing to assign: no assign or cost launch
     TWTML_HIP_CHECK(hipEventRecord(ev1_, s));
     TWTML_HIP_CHECK(hipStreamSynchronize(s));
     TWTML_HIP_CHECK(hipEventElapsedTime(&res.ms, ev0_, ev1_));
-    return res;
+    return 0;
   }
   upload_factors(scaler_mode, n, std, res.std, s);
   auto* refine_cnt = reinterpret_cast<unsigned long long*>(prep_.counters + 5);
@@ -205,6 +205,18 @@ KMScoreResult KMEngine::score(int slot, bool apply_filter, int scaler_mode, cons
   double* cost = cost_part_ + cost_parts_;
   launch_km_cost(X_, fac64_, labels_, centers_, prep_.counters, n, k, d, dp_, dist2_, cost_part_, cost,
                  lhist_, s);
+  *cost_out = cost;
+  return n;
+}
+
+KMScoreResult KMEngine::score(int slot, bool apply_filter, int scaler_mode, const double* std) {
+  TraceRange tr("twtml.km.score");
+  KMScoreResult res;
+  double* cost = nullptr;
+  const int64_t n = score_kernels("score()", slot, apply_filter, scaler_mode, std, res, &cost);
+  if (n == 0) return res;
+  hipStream_t s = compute_;
+  const int k = cfg_.k;
   TWTML_HIP_CHECK(hipEventRecord(ev1_, s));
   const size_t R = size_t(cfg_.max_rows), un = size_t(n);
   auto* h_rows = static_cast<int64_t*>(score_host_.get());
@@ -224,6 +236,49 @@ KMScoreResult KMEngine::score(int slot, bool apply_filter, int scaler_mode, cons
   res.cost = *h_cost;
   res.sizes.assign(h_sizes, h_sizes + k);
   TWTML_HIP_CHECK(hipEventElapsedTime(&res.ms, ev0_, ev1_));
+  return res;
+}
+
+void KMEngine::ensure_top() {
+  if (top_sc_.out) return;
+  top_host_.alloc(sizeof(int64_t) * (top_out_words(kTopNMax) + 1 + size_t(cfg_.k)), hipHostMallocDefault);
+  top_sc_ = top_scratch_carve(arena_.alloc<int64_t>(top_scratch_words()));
+}
+
+KMTopResult KMEngine::top(int slot, bool apply_filter, int scaler_mode, const double* std, int n, bool largest) {
+  if (n < 1 || n > kTopNMax)
+    throw std::invalid_argument("top(): n must be in [1, " + std::to_string(kTopNMax) + "]; use score() for every row");
+  TraceRange tr("twtml.km.top");
+  KMTopResult res;
+  double* cost = nullptr;
+  const int64_t ns = score_kernels("top()", slot, apply_filter, scaler_mode, std, res.batch, &cost);
+  res.top.n_raw = res.batch.n_raw;
+  if (ns == 0) return res;
+  ensure_top();
+  hipStream_t s = compute_;
+  const size_t k = size_t(cfg_.k);
+  launch_top_select(dist2_, prep_.kept, labels_, prep_.counters, cfg_.max_rows, n, largest, top_sc_, s);
+  TWTML_HIP_CHECK(hipEventRecord(ev1_, s));
+  int64_t* h = top_host_.get();
+  int64_t* h_cost = h + top_out_words(kTopNMax);
+  int64_t* h_sizes = h_cost + 1;
+  TWTML_HIP_CHECK(hipMemcpyAsync(h, top_sc_.out, sizeof(int64_t) * top_out_words(n), hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipMemcpyAsync(h_cost, cost, sizeof(double), hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipMemcpyAsync(h_sizes, lhist_, sizeof(int64_t) * k, hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipStreamSynchronize(s));
+  TopResult& t = res.top;
+  t.n_scored = h[kTopCnt];
+  t.n_top = h[kTopNTop];
+  t.n_nan = h[kTopNNan];
+  if (t.n_scored != ns || t.n_top < 0 || t.n_top > n || t.n_nan < 0 || t.n_top + t.n_nan > ns)
+    throw std::runtime_error("top(): the result block's counts are out of range");
+  t.bits = h + kTopHead;
+  t.rows = h + kTopHead + n;
+  t.payload = h + kTopHead + 2 * size_t(n);
+  std::memcpy(&res.batch.cost, h_cost, sizeof(double));
+  res.batch.sizes.assign(h_sizes, h_sizes + k);
+  TWTML_HIP_CHECK(hipEventElapsedTime(&res.batch.ms, ev0_, ev1_));
+  t.top_ms = res.batch.ms;
   return res;
 }
 
@@ -428,6 +483,27 @@ void bind_kmeans(py::module_& m) {
       }, py::arg("slot"), py::arg("apply_filter") = true, py::arg("scaler_mode") = 0, py::arg("std") = py::none(),
          "inference only: labels, squared distances, cost and cluster sizes of the batch in `slot` under the "
          "current model; scaler_mode 0 per-batch fit, 1 the given std[d], 2 none")
+      .def("top", [](KMEngine& e, int slot, bool apply_filter, int scaler_mode,
+                     std::optional<py::array_t<double, py::array::c_style | py::array::forcecast>> std, int n,
+                     bool largest) {
+        if (scaler_mode == kKmScalerGiven && (!std || std->size() != e.d()))
+          throw std::invalid_argument("top(): the given scaler needs d stds");
+        KMTopResult r;
+        {
+          const double* sp = std ? std->data() : nullptr;
+          py::gil_scoped_release nogil;
+          r = e.top(slot, apply_filter, scaler_mode, sp, n, largest);
+        }
+        py::dict out = top_dict(r.top);
+        out["n_scored"] = r.batch.n_scored;
+        out["cost"] = r.batch.cost;
+        out["sizes"] = py::array_t<int64_t>(py::ssize_t(r.batch.sizes.size()), r.batch.sizes.data());
+        out["std"] = py::array_t<double>(py::ssize_t(r.batch.std.size()), r.batch.std.data());
+        return out;
+      }, py::arg("slot"), py::arg("apply_filter") = true, py::arg("scaler_mode") = 0, py::arg("std") = py::none(),
+         py::arg("n") = 1, py::arg("largest") = true,
+         "inference only: the n rows farthest from (largest) or closest to their centres, selected on the device: "
+         "rows, values (squared distances), payload (labels), with the batch's cost, sizes and std")
       .def_static("cost_shape", [](int dp) {
         const KmCostShape sh = km_cost_shape(dp);
         return py::make_tuple(sh.lanes_per_row, sh.rows_per_wave, sh.rows_per_wg);

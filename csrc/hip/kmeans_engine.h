@@ -53,6 +53,14 @@ struct KMScoreResult {
   float ms = 0.f;                   // device time of the kernels (events)
 };
 
+// top(): score()'s batch-wide outputs and the n best rows by squared distance
+// (top.payload: their labels).  top's arrays point into the engine's pinned
+// block: valid until the next top().
+struct KMTopResult {
+  KMScoreResult batch;   // n_raw, n_scored, cost, sizes, std, ms (through the selection); no per-row arrays
+  TopResult top;
+};
+
 class KMEngine {
  public:
   KMEngine(int device, const KMConfig& cfg, std::shared_ptr<Comm> comm);
@@ -67,6 +75,12 @@ class KMEngine {
   // communicator untouched; reuses the batch scratch of process() (both end in
   // a stream sync, so they never overlap).
   KMScoreResult score(int slot, bool apply_filter, int scaler_mode, const double* std);
+  // The n rows (1 <= n <= kTopNMax) farthest from their centres (largest; else
+  // the closest): score() up to and including the cost pass, then the
+  // selection of topn.hip over the squared distances with the kept row ids
+  // and the labels as payload.  Only the result block, the cost, the sizes and
+  // the stds leave the device; no communicator is called.
+  KMTopResult top(int slot, bool apply_filter, int scaler_mode, const double* std, int n, bool largest);
   // Forget a submitted batch that will not be processed: waits for its H2D
   // (the staging buffer may then be rewritten); the copy stream keeps the
   // slot's next H2D in order behind it.
@@ -95,6 +109,13 @@ class KMEngine {
   // the n rows fitted); `std` receives the d stds used (none: empty).
   void upload_factors(int mode, int64_t n, const double* given, std::vector<double>& std, hipStream_t s);
   void ensure_score();
+  void ensure_top();
+  // What score() and top() share: filter .. the cost pass of the batch in
+  // `slot`, ev0_ recorded first.  Returns the scored rows n (res.n_raw,
+  // n_scored, sizes and std filled) and the device cost word; n == 0: nothing
+  // was assigned, ev1_ is recorded and the stream synchronised.
+  int64_t score_kernels(const char* who, int slot, bool apply_filter, int scaler_mode, const double* std,
+                        KMScoreResult& res, double** cost);
   int device_;
   KMConfig cfg_;
   int d_, dp_;
@@ -126,8 +147,13 @@ class KMEngine {
   double *dist2_ = nullptr, *cost_part_ = nullptr;   // [R] | [partials + 1]: the partials, then the cost
   size_t cost_parts_ = 0;
   Pinned<void> score_host_;            // [R] rows | [R] dist2 | cost | [k] sizes | [R] labels
+  // top() only, allocated by its first call
+  TopScratch top_sc_{};
+  Pinned<int64_t> top_host_;           // result block of kTopNMax | cost | [k] sizes
 };
 
 void bind_kmeans(pybind11::module_& m);
+// A selection's result as a dict of arrays owned by the caller (bindings.cpp).
+pybind11::dict top_dict(const TopResult& r);
 
 }  // namespace twtml

@@ -41,13 +41,28 @@ the labels, each row's squared distance to its centre and the batch's cost
                       ``--predictOut`` (both passes run).  A k-means model with
                       ``--evalOut`` is a usage error (exit code 2): ``cost`` is its
                       metric already.  Nothing is posted to twtml-web.
+``--top N``           with ``--topOut DIR``: the N (1..4096) highest-scored tweets of every
+                      batch (``engine.top_batch``; on ``rocm[N]`` the exact radix select
+                      of ``csrc/hip/topn.hip`` behind the scoring kernels: N entries come
+                      back, not the predictions), ``--topSmallest``: the lowest.  Per
+                      batch one line of ``top.jsonl`` -- seq, batch time, count, n_nan, ms
+                      and ``entries``, best first, ties by row: ``row``, ``value``, the
+                      row's ``retweetCount`` and ``text``; logistic models select on the
+                      margin (``value``) and add ``probability``; k-means models select
+                      the rows farthest from their centres (``dist2``, ``label``) -- and
+                      at the end ``summary.json``, the best N of the stream
+                      (``models/topn.TopNMerger``; entries carry ``seq``).  May be
+                      combined with ``--predictOut`` and ``--evalOut`` (each runs its own
+                      pass; give each its own directory).  ``--top`` without ``--topOut``
+                      or N outside 1..4096 is a usage error (exit code 2).
 ``--scalerStd FILE``  k-means: ``.npy`` of d column stds, the frozen scaler
 ``--numBatches N``    stop after N batches
 
 With more than one rank (``rocm[N>1]``, one process per GPU) every rank
 scores its own shard of the stream and writes its own files, suffixed
 ``_r<rank>``; scoring needs no collective.  The ranks' ``metrics_r<rank>.jsonl``
-accumulators combine exactly with ``EvalAccumulator.from_dict`` + ``merge``.
+accumulators combine exactly with ``EvalAccumulator.from_dict`` + ``merge``,
+and the lines of their ``top_r<rank>.jsonl`` with ``TopNMerger.add``.
 """
 from __future__ import annotations
 
@@ -70,7 +85,7 @@ from ..utils.logging import setup_logging
 from ._common import exit_on_sigterm
 from .linear_regression import build_engine
 
-__all__ = ["main", "ScoreJob", "KMeansScoreJob", "EvalJob", "build_kmeans_scorer"]
+__all__ = ["main", "ScoreJob", "KMeansScoreJob", "EvalJob", "TopJob", "build_kmeans_scorer"]
 
 log = logging.getLogger("com.giorgioinf.twtml.spark.Score")
 APP_NAME = "twitter-stream-ml-score"
@@ -196,6 +211,71 @@ class EvalJob:
             f.write("\n")
 
 
+class TopJob:
+    """Per-batch logic of ``--top N``: the batch's N best rows
+    (``engine.top_batch``) as one line of ``top.jsonl``, the best N of the
+    whole stream (``models/topn.TopNMerger``) in ``summary.json`` at the end.
+    ``kind``: ``"linear"`` (value = prediction), ``"logistic"`` (value =
+    margin; ``probability`` added on the host with the model class's link) or
+    ``"kmeans"`` (value = ``dist2``, with ``label``)."""
+
+    def __init__(self, engine, n: int, largest: bool, out_dir: str, kind: str = "linear", rank: int = 0,
+                 world: int = 1, **engine_kw):
+        from ..models.topn import TopNMerger
+        self.engine = engine
+        self.n, self.largest, self.kind = int(n), bool(largest), kind
+        self.kw = engine_kw
+        self.out_dir = out_dir
+        self.suffix = f"_r{rank}" if world > 1 else ""
+        self.batches = 0
+        self.merger = TopNMerger(self.n, self.largest)
+        os.makedirs(out_dir, exist_ok=True)
+        self._jsonl = open(os.path.join(out_dir, f"top{self.suffix}.jsonl"), "a", encoding="utf-8")
+
+    def _entries(self, raw, res) -> List[dict]:
+        from ..records.batch import RETWEET_COUNT
+        rows = [int(r) for r in res["rows"]]
+        out = [{"row": r, "value": float(v), "retweetCount": int(raw.scalars[RETWEET_COUNT][r]),
+                "text": raw.text_of(r)} for r, v in zip(rows, res["values"])]
+        if self.kind == "logistic":
+            from ..models.logistic_regression import sigmoid
+            for e, p in zip(out, sigmoid(np.asarray(res["values"], np.float64))):
+                e["probability"] = float(p)
+        elif self.kind == "kmeans":
+            for e, lab in zip(out, res["labels"]):
+                e["dist2"] = e["value"]
+                e["label"] = int(lab)
+        return out
+
+    def on_batch(self, rdd, time_ms: int) -> None:
+        raw = rdd.raw
+        t0 = time.perf_counter()
+        res = self.engine.top_batch(raw, self.n, largest=self.largest, **self.kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        entries = self._entries(raw, res)
+        seq = self.batches
+        self.batches += 1
+        self.merger.add(seq, [e["value"] for e in entries], [e["row"] for e in entries], int(res["n_nan"]),
+                        [{k: v for k, v in e.items() if k not in ("row", "value")} for e in entries])
+        rec = {"seq": seq, "batch_time_ms": int(time_ms), "count": int(res["n_scored"]), "n_nan": int(res["n_nan"]),
+               "ms": round(ms, 3), "top_ms": round(float(res.get("top_ms", 0.0)), 3), "entries": entries}
+        if self.kind == "kmeans":
+            rec["cost"] = float(res["cost"])
+        self._jsonl.write(json.dumps(rec) + "\n")
+        self._jsonl.flush()
+
+    def close(self) -> None:
+        if self._jsonl is None:
+            return
+        self._jsonl.close()
+        self._jsonl = None
+        summary = {"batches": self.batches, "n": self.n, "largest": self.largest, "n_nan": self.merger.n_nan,
+                   "entries": self.merger.result()}
+        with open(os.path.join(self.out_dir, f"summary{self.suffix}.json"), "w", encoding="utf-8") as f:
+            json.dump(summary, f)
+            f.write("\n")
+
+
 def build_kmeans_scorer(conf, centers: np.ndarray, weights: np.ndarray, device: Optional[int]):
     """The engine that scores with a loaded k-means model: a DeviceKMeans on
     ``device`` (no communicator: every rank scores its own shard) or, with
@@ -248,6 +328,12 @@ def main(argv: Optional[List[str]] = None) -> int:
         print("twtml-score: --evalOut does not apply to a k-means model: its metric is the cost that "
               "--predictOut already reports", file=sys.stderr)
         return 2
+    if conf.top or conf.topOut or conf.topSmallest:
+        from ..models.topn import TOPN_MAX
+        if not conf.topOut or not 1 <= conf.top <= TOPN_MAX:
+            print(f"twtml-score: --top N needs N in 1..{TOPN_MAX} and --topOut <dir> (got --top {conf.top}, "
+                  f"--topOut {conf.topOut!r}); --predictOut writes every row", file=sys.stderr)
+            return 2
     scaler = "batch"
     if km is not None:
         text_dims = (w.shape[1] if w.ndim == 2 else 0) - 2
@@ -297,10 +383,21 @@ def main(argv: Optional[List[str]] = None) -> int:
     else:
         job = ScoreJob(engine, conf.predictOut, rank, world, output)
     ev = EvalJob(engine, conf.evalOut, rank, world) if conf.evalOut else None
-    if ev is None or conf.predictOut:
+    top = None
+    if conf.top:
+        if km is not None:
+            top = TopJob(engine, conf.top, not conf.topSmallest, conf.topOut, "kmeans", rank, world,
+                         apply_filter=True, scaler=scaler, **job._kw)
+        else:
+            top = TopJob(engine, conf.top, not conf.topSmallest, conf.topOut, "logistic" if logistic else "linear",
+                         rank, world, apply_filter=False)
+    score = (ev is None and top is None) or bool(conf.predictOut)
+    if score:
         stream.foreachRDD(job.on_batch)
     if ev is not None:
         stream.foreachRDD(ev.on_batch)
+    if top is not None:
+        stream.foreachRDD(top.on_batch)
     ssc.start()
     try:
         ssc.awaitTermination()
@@ -311,9 +408,13 @@ def main(argv: Optional[List[str]] = None) -> int:
         job.close()
         if ev is not None:
             ev.close()
+        if top is not None:
+            top.close()
     if ev is not None:
         log.info("evaluated %d batches", ev.batches)
-    if ev is None or conf.predictOut:
+    if top is not None:
+        log.info("selected the top %d of %d batches", top.n, top.batches)
+    if score:
         log.info("scored %d tweets in %d batches", job.scored, job.batches)
     return 0
 

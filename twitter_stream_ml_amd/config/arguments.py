@@ -19,7 +19,8 @@ short letters keep their meaning): ``--source``, ``--batchSize``,
 ``--numBatches``, ``--hash``, ``--checkpoint``, ``--checkpointInterval``,
 ``--resume``, ``--sourceRate``, ``--plotPoints``, ``--legacyNumTextFeatures``,
 ``--batchTimeout``, ``--checkReplicas``, ``--model``, ``--predictOut``,
-``--scalerStd``, ``--evalOut``.
+``--scalerStd``, ``--evalOut``, ``--top``, ``--topSmallest`` (no value),
+``--topOut``.
 The master accepts, besides Spark's ``local``, ``local[N]``, ``local[*]``
 (CPU plumbing engine, fp64), the device masters ``rocm``, ``rocm[N]``,
 ``rocm[*]`` and ``rocm:0,1,...`` (HIP engine, one process per GPU).
@@ -143,6 +144,8 @@ _EXT_FLAGS = {
     "--predictOut": ("predictOut", str),
     "--scalerStd": ("scalerStd", str),
     "--evalOut": ("evalOut", str),
+    "--top": ("top", int),
+    "--topOut": ("topOut", str),
     # apps/logistic_regression.py (and apps/score.py with a logistic model)
     "--labelThreshold": ("labelThreshold", int),
     "--threshold": ("threshold", float),
@@ -207,6 +210,9 @@ class ConfArguments:
         self.predictOut = ""   # apps/score.py: directory of the per-batch prediction files
         self.scalerStd = ""    # apps/score.py, k-means models: .npy of d column stds (frozen scaler)
         self.evalOut = ""      # apps/score.py: directory of the held-out metrics (metrics.jsonl, summary.json)
+        self.top = 0           # apps/score.py: select the N best rows of every batch (0: off)
+        self.topSmallest = False   # ... the lowest values instead of the highest
+        self.topOut = ""       # apps/score.py: directory of top.jsonl and summary.json
         # apps/logistic_regression.py: label = retweetCount >= labelThreshold (-1: middle of the
         # filter range), class 1 when the probability exceeds threshold
         self.labelThreshold = c.getInt("labelThreshold") if c.hasPath("labelThreshold") else -1
@@ -254,6 +260,10 @@ Usage: twtml-spark [options]
   --evalOut <dir>                                 scoring driver, linear / logistic models: evaluate the stream
                                                   against its retweet counts (metrics.jsonl per batch, summary.json;
                                                   logistic: AUC with its tie bound, class 1 is --labelThreshold)
+  --top <N>  [--topSmallest]  --topOut <dir>      scoring driver: the N (1..4096) highest-scored tweets of every
+                                                  batch (k-means: the N farthest from their centres), selected on
+                                                  the device; --topSmallest: the lowest.  top.jsonl per batch,
+                                                  summary.json: the best N of the stream
   --scalerStd <file.npy>                          scoring driver, k-means models: the d column stds of a
                                                   frozen scaler (default: a StandardScaler fitted per batch)
   --labelThreshold <n>  --threshold <p>           logistic driver (apps.logistic_regression / twtml-logistic):
@@ -302,6 +312,10 @@ Usage: twtml-spark [options]
                 self.printUsage(0)
             if flag == "--legacyNumTextFeatures":
                 self.honourNumTextFeatures = False
+                i += 1
+                continue
+            if flag == "--topSmallest":
+                self.topSmallest = True
                 i += 1
                 continue
             if flag in _FLAG_LOOKUP and i + 1 < len(lst):

@@ -266,3 +266,20 @@ class CpuKMeans:
         return {"n_raw": int(raw.n), "n_scored": int(X.shape[0]), "rows": rows, "pred": pred.astype(np.int32),
                 "dist2": dist2, "cost": float(dist2.sum()), "sizes": np.bincount(pred, minlength=k).astype(np.int64),
                 "std": std, "score_ms": ms, "wall_ms": ms}
+
+    def top_batch(self, raw: RawBatch, n: int, text_dims: int, largest: bool = True, apply_filter: bool = True,
+                  scaler="batch") -> Dict[str, object]:
+        """The n rows farthest from their centres (``largest``: the batch's
+        outliers; else the closest), the contract of ``DeviceKMeans.top_batch``:
+        ``models/topn.top_n`` of this engine's own ``predict_batch`` ``dist2``,
+        with the rows' labels and the batch's ``cost``, ``sizes`` and ``std``."""
+        from .topn import check_n, top_result
+        check_n(n)
+        t0 = time.perf_counter()
+        res = self.predict_batch(raw, text_dims, apply_filter=apply_filter, scaler=scaler)
+        out = top_result(res["dist2"], res["rows"], n, largest)
+        labels = np.asarray(res["pred"], np.int32)[np.searchsorted(res["rows"], out["rows"])]
+        ms = (time.perf_counter() - t0) * 1e3
+        out.update(dist2=out["values"], labels=labels, cost=res["cost"], sizes=res["sizes"], std=res["std"],
+                   n_raw=res["n_raw"], n_scored=res["n_scored"], top_ms=ms, wall_ms=ms)
+        return out

@@ -209,6 +209,21 @@ class CpuLinearRegression:
         out.update(n_raw=raw.n, n_scored=int(res["n_scored"]), eval_ms=ms, wall_ms=ms)
         return out
 
+    def top_batch(self, raw: RawBatch, n: int, largest: bool = True, apply_filter: bool = False,
+                  now_ms: Optional[int] = None) -> Dict[str, object]:
+        """The n best rows of a raw batch (the contract of
+        ``DeviceLinearRegression.top_batch``): ``models/topn.top_n`` of this
+        engine's own ``predict_batch``."""
+        import time
+        from .topn import check_n, top_result
+        check_n(n)
+        t0 = time.perf_counter()
+        res = self.predict_batch(raw, apply_filter=apply_filter, now_ms=now_ms)
+        out = top_result(res["pred"], res["rows"], n, largest)
+        ms = (time.perf_counter() - t0) * 1e3
+        out.update(n_raw=raw.n, n_scored=int(res["n_scored"]), top_ms=ms, wall_ms=ms)
+        return out
+
     def synchronize(self) -> None:
         pass
 

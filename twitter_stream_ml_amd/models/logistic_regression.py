@@ -306,6 +306,22 @@ class CpuLogisticRegression:
         out.update(n_raw=raw.n, n_scored=int(res["n_scored"]), eval_ms=ms, wall_ms=ms)
         return out
 
+    def top_batch(self, raw: RawBatch, n: int, largest: bool = True, apply_filter: bool = False,
+                  now_ms: Optional[int] = None) -> Dict[str, object]:
+        """The n best rows of a raw batch by margin (the contract of
+        ``DeviceLogisticRegression.top_batch``): ``models/topn.top_n`` of this
+        engine's own ``predict_batch(output="margin")``.  ``values`` are
+        margins; ``link`` maps them to probabilities."""
+        import time
+        from .topn import check_n, top_result
+        check_n(n)
+        t0 = time.perf_counter()
+        res = self.predict_batch(raw, apply_filter=apply_filter, now_ms=now_ms, output="margin")
+        out = top_result(res["pred"], res["rows"], n, largest)
+        ms = (time.perf_counter() - t0) * 1e3
+        out.update(n_raw=raw.n, n_scored=int(res["n_scored"]), top_ms=ms, wall_ms=ms)
+        return out
+
     def synchronize(self) -> None:
         pass
 

@@ -186,6 +186,41 @@ class DeviceKMeans:
         r["wall_ms"] = (time.perf_counter() - t0) * 1e3
         return r
 
+    # ---- top-N (KMEngine::top, csrc/hip/topn.hip) --------------------------
+    def top_batch(self, raw: RawBatch, n: int, largest: bool = True, apply_filter: bool = True,
+                  scaler="batch") -> Dict[str, object]:
+        """The n rows of one raw micro-batch farthest from their centres
+        (``largest``, the default: the batch's outliers; else the closest),
+        selected on the device (the contract of ``models/topn.py``):
+        ``predict_batch``'s passes, then the selection over ``dist2`` --
+        ``rows``, ``dist2`` (= ``values``) and ``labels`` of the selected rows,
+        best first, equal distances by ascending row; the batch's ``cost``,
+        ``sizes`` and ``std``; ``n_top``, ``n_nan``, ``n_raw``, ``n_scored``,
+        ``top_ms`` (device time) and ``wall_ms``.  Only these leave the device.
+        ``1 <= n <= 4096``.  Arguments and guarantees are ``predict_batch``'s."""
+        from ..models.topn import check_n, empty_top
+        n = check_n(n)
+        mode, std = scaler_mode(scaler, self.dim, bool(self.cfg.scale))
+        if raw.n == 0:                # nothing is staged or launched
+            e = empty_score(0, self.cfg.k, std)
+            return {**empty_top(), "dist2": np.zeros(0, np.float64), "labels": np.zeros(0, np.int32),
+                    "cost": 0.0, "sizes": e["sizes"], "std": e["std"], "n_raw": 0, "n_scored": 0,
+                    "top_ms": 0.0, "wall_ms": 0.0}
+        t0 = time.perf_counter()
+        slot = self._pipe.free_slot()
+        try:
+            self.submit(self._stage(slot, raw), slot)
+            r = self._eng.top(int(slot), bool(apply_filter), mode, std, n, bool(largest))
+        finally:
+            self._pipe.score_done(slot)
+        values = np.asarray(r["values"])
+        return {"rows": np.asarray(r["rows"]), "values": values, "dist2": values,
+                "labels": np.asarray(r["payload"], np.int32), "n_top": int(r["n_top"]), "n_nan": int(r["n_nan"]),
+                "cost": float(r["cost"]), "sizes": np.asarray(r["sizes"]),
+                "std": std.copy() if std is not None else (np.asarray(r["std"]) if len(r["std"]) else None),
+                "n_raw": int(r["n_raw"]), "n_scored": int(r["n_scored"]), "top_ms": float(r["top_ms"]),
+                "wall_ms": (time.perf_counter() - t0) * 1e3}
+
     @property
     def h2d_bytes(self) -> int:
         """Host-to-device bytes submitted so far (every copy of every batch)."""

@@ -483,6 +483,39 @@ class DeviceLinearRegression:
             out.update({k: float(dw[j]) for j, k in enumerate(metrics.REGRESSION_SUMS)})
         return out
 
+    # ---- top-N (csrc/hip/topn.hip) -----------------------------------------
+    def top_batch(self, raw: RawBatch, n: int, largest: bool = True, apply_filter: bool = False,
+                  now_ms: Optional[int] = None) -> Dict[str, object]:
+        """The n best rows of one raw micro-batch under the current weights,
+        selected on the device (the contract of ``models/topn.py``):
+        ``predict_batch``'s margins ``x . w``, then an exact radix select and
+        sort behind them -- ``rows`` (int64 raw row ids) and ``values`` (their
+        fp64 margins), best first (``largest``: descending), equal margins by
+        ascending row, NaN margins never; ``n_top`` = ``min(n, n_scored -
+        n_nan)``, ``n_nan``, ``n_raw``, ``n_scored``, ``top_ms`` (device time,
+        filter through the selection) and ``wall_ms``.  Only the n entries
+        leave the device.  The logistic engine selects on the margin too: it
+        is monotone in the probability and still separates rows whose
+        probability has saturated.  ``1 <= n <= 4096``.  Staging and
+        guarantees are ``predict_batch``'s."""
+        from ..models.topn import check_n, empty_top
+        n = check_n(n)
+        self.staging(0)._check(raw)
+        if raw.n == 0:                # nothing is staged or launched
+            return {**empty_top(), "n_raw": 0, "n_scored": 0, "top_ms": 0.0, "wall_ms": 0.0}
+        slot = self._pipe.free_slot()
+        try:
+            hb = self.staging(slot).load(raw, self.cfg.ingest)
+            self._eng.submit(hb._hb, int(hb.n), int(hb.bytes), int(slot), int(hb.ext_text),
+                             int(hb.batch_time_ms), False)
+            r = self._eng.top(int(slot), int(raw.batch_time_ms if now_ms is None else now_ms),
+                              bool(apply_filter), n, bool(largest))
+        finally:
+            self._pipe.score_done(slot)
+        return {"rows": np.asarray(r["rows"]), "values": np.asarray(r["values"]), "n_top": int(r["n_top"]),
+                "n_nan": int(r["n_nan"]), "n_raw": int(r["n_raw"]), "n_scored": int(r["n_scored"]),
+                "top_ms": float(r["top_ms"]), "wall_ms": float(r["wall_ms"])}
+
     @property
     def h2d_bytes(self) -> int:
         """Host-to-device bytes submitted so far (every copy of every batch)."""
