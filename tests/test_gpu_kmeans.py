@@ -325,8 +325,12 @@ def test_kmeans_config4_bench_scale_matches_oracle(hip_module):
 @pytest.mark.parametrize("text_dims", [1, 8, 14, 62, 64, 65, 126])
 def test_kmeans_features_exact(hip_module, text_dims):
     """The device feature rows (before scaling) equal the host featurizer's
-    exactly: the lane-private histogram kernel (text_dims <= 64, config 4's
-    62) and the shared-histogram kernel above it; padding columns are 0."""
+    exactly.  Every width here (<= kKmChunkDims = 256, config 4's 62 among
+    them) takes the balanced chunk kernel k_km_features_bal: 16 rows staged
+    back to back in LDS, their bigrams split evenly over the 64 lanes, u16
+    histogram halves.  The generic one-wave-per-row k_km_features (> 256) and
+    the dispatch boundary are compared in test_gpu_text_atlas.py.  Padding
+    columns are 0."""
     from twitter_stream_ml_amd.ops.kmeans_engine import DeviceKMeans
     dev = DeviceKMeans(_cfg(16, text_dims, seed=3), device=0)
     for raw in _batches(n=2, rows=6000, seed=33, unicode_fraction=0.4):
