@@ -15,6 +15,7 @@
 #include <stdexcept>
 
 #include "kmeans_kernels.h"
+#include "silhouette.h"
 
 namespace py = pybind11;
 
@@ -282,6 +283,126 @@ KMTopResult KMEngine::top(int slot, bool apply_filter, int scaler_mode, const do
   return res;
 }
 
+void KMEngine::ensure_sil() {
+  if (sil_mean_) return;
+  const size_t R = size_t(cfg_.max_rows), k = size_t(cfg_.k), d = size_t(d_);
+  sil_mean_ = arena_.alloc<double>(k * d);
+  sil_dev2_ = arena_.alloc<double>(R);
+  sil_part_ = arena_.alloc<double>(cost_parts_ + 1);
+  sil_W_ = arena_.alloc<double>(k);
+  sil_V_ = arena_.alloc<double>(k);
+  sil_mu32_ = arena_.alloc<float>(k * size_t(dp_));
+  sil_B_ = arena_.alloc<float>(k);
+  sil_wacc_ = arena_.alloc<unsigned long long>(2 * k);
+  sil_hist_ = arena_.alloc<int64_t>(k + 1);
+  sil_sizes_ = arena_.alloc<int64_t>(k);
+  sil_words_ = arena_.alloc<int64_t>(sil_words(cfg_.k));
+  sil_nb_ = arena_.alloc<int32_t>(R);
+  sil_a_ = arena_.alloc<double>(R);
+  sil_b_ = arena_.alloc<double>(R);
+  sil_s_ = arena_.alloc<double>(R);
+  sil_host_.alloc(sizeof(int64_t) * (sil_words(cfg_.k) + 1 + k) + R * (sizeof(int64_t) + 3 * sizeof(double) +
+                                                                         2 * sizeof(int32_t)),
+                  hipHostMallocDefault);
+}
+
+KMSilResult KMEngine::silhouette(int slot, bool apply_filter, int scaler_mode, const double* std, bool per_row) {
+  TraceRange tr("twtml.km.silhouette");
+  KMSilResult res;
+  res.per_row = per_row;
+  const int k = cfg_.k, d = d_;
+  res.n.assign(size_t(k), 0);
+  res.s_fix.assign(size_t(k), 0);
+  double* cost = nullptr;
+  const int64_t n = score_kernels("silhouette()", slot, apply_filter, scaler_mode, std, res.batch, &cost);
+  if (n == 0) return res;
+  hipStream_t s = compute_;
+  ensure_sil();
+  const size_t R = size_t(cfg_.max_rows), un = size_t(n), nw = sil_words(k);
+  auto* h_words = static_cast<int64_t*>(sil_host_.get());
+  auto* h_cost = reinterpret_cast<double*>(h_words + nw);
+  auto* h_sizes = reinterpret_cast<int64_t*>(h_cost + 1);
+  auto* h_rows = h_sizes + k;
+  auto* h_a = reinterpret_cast<double*>(h_rows + R);
+  double *h_b = h_a + R, *h_s = h_b + R;
+  auto* h_labels = reinterpret_cast<int32_t*>(h_s + R);
+  int32_t* h_nb = h_labels + R;
+  // the sizes decide what runs: fewer than two non-empty clusters is undefined
+  TWTML_HIP_CHECK(hipMemcpyAsync(h_cost, cost, sizeof(double), hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipMemcpyAsync(h_sizes, lhist_, sizeof(int64_t) * size_t(k), hipMemcpyDeviceToHost, s));
+  TWTML_HIP_CHECK(hipStreamSynchronize(s));
+  res.batch.cost = *h_cost;
+  res.batch.sizes.assign(h_sizes, h_sizes + k);
+  int64_t total = 0;
+  for (int c = 0; c < k; ++c) {
+    total += h_sizes[c];
+    res.nonempty += h_sizes[c] > 0;
+  }
+  if (total != n) throw std::runtime_error("silhouette(): labels outside the model's clusters (NaN centres?)");
+  if (n > kSilMaxRows)
+    throw std::invalid_argument("silhouette(): a batch of more than " + std::to_string(kSilMaxRows) + " scored rows");
+  const bool defined = res.nonempty >= 2;
+  if (defined) {
+    int64_t* mx = qmom_;   // the batch scaler left the column maxima here; the other modes fit them now
+    if (scaler_mode != kKmScalerBatch) {
+      TWTML_HIP_CHECK(hipMemsetAsync(mx, 0, sizeof(int64_t) * size_t(d), s));
+      launch_km_colmax(X_, prep_.counters, d, dp_, mx, cfg_.max_rows, s);
+    }
+    double* counts = sums_ + size_t(k) * d;
+    TWTML_HIP_CHECK(hipMemsetAsync(sums_i_, 0, sizeof(int64_t) * (size_t(k) * d + k), s));
+    launch_km_cluster_sums(X_, mx, labels_, prep_.counters, k, d, dp_, sil_hist_, order_, sums_i_, cfg_.max_rows, s,
+                           &scan_excl_launch);
+    launch_km_sums_f64(sums_i_, mx, fac64_, k, d, sums_, counts, s);
+    launch_sil_means(sums_, counts, k, d, sil_mean_, s);
+    launch_km_cost(X_, fac64_, labels_, sil_mean_, prep_.counters, n, k, d, dp_, sil_dev2_, sil_part_,
+                   sil_part_ + cost_parts_, sil_sizes_, s);
+    launch_sil_stats(sil_dev2_, labels_, n, k, d, dp_, sil_mean_, sil_sizes_, sil_wacc_, sil_wacc_ + k, sil_W_,
+                     sil_V_, sil_mu32_, sil_B_, s);
+    TWTML_HIP_CHECK(hipMemsetAsync(sil_words_, 0, sizeof(int64_t) * nw, s));
+    launch_sil_neighbor(X_, fac32_, fac64_, labels_, sil_dev2_, n, k, d, dp_, sil_mean_, sil_mu32_, sil_B_, sil_V_,
+                        sil_W_, sil_sizes_, cfg_.mfma != 0, sil_words_, per_row ? sil_nb_ : nullptr, sil_a_, sil_b_,
+                        sil_s_, s);
+    TWTML_HIP_CHECK(hipEventRecord(ev1_, s));
+    TWTML_HIP_CHECK(hipMemcpyAsync(h_words, sil_words_, sizeof(int64_t) * nw, hipMemcpyDeviceToHost, s));
+  } else {
+    TWTML_HIP_CHECK(hipEventRecord(ev1_, s));
+    if (per_row) {   // no neighbour, a = b = s = 0
+      TWTML_HIP_CHECK(hipMemsetAsync(sil_nb_, 0xff, sizeof(int32_t) * un, s));
+      for (double* p : {sil_a_, sil_b_, sil_s_}) TWTML_HIP_CHECK(hipMemsetAsync(p, 0, sizeof(double) * un, s));
+    }
+  }
+  if (per_row) {
+    TWTML_HIP_CHECK(hipMemcpyAsync(h_rows, prep_.kept, sizeof(int64_t) * un, hipMemcpyDeviceToHost, s));
+    TWTML_HIP_CHECK(hipMemcpyAsync(h_labels, labels_, sizeof(int32_t) * un, hipMemcpyDeviceToHost, s));
+    TWTML_HIP_CHECK(hipMemcpyAsync(h_nb, sil_nb_, sizeof(int32_t) * un, hipMemcpyDeviceToHost, s));
+    TWTML_HIP_CHECK(hipMemcpyAsync(h_a, sil_a_, sizeof(double) * un, hipMemcpyDeviceToHost, s));
+    TWTML_HIP_CHECK(hipMemcpyAsync(h_b, sil_b_, sizeof(double) * un, hipMemcpyDeviceToHost, s));
+    TWTML_HIP_CHECK(hipMemcpyAsync(h_s, sil_s_, sizeof(double) * un, hipMemcpyDeviceToHost, s));
+  }
+  TWTML_HIP_CHECK(hipStreamSynchronize(s));
+  TWTML_HIP_CHECK(hipEventElapsedTime(&res.batch.ms, ev0_, ev1_));
+  if (defined) {
+    res.n.assign(h_words, h_words + k);
+    res.s_fix.assign(h_words + k, h_words + 2 * k);
+    res.n_single = h_words[2 * k];
+    int64_t counted = 0;
+    for (int c = 0; c < k; ++c) counted += res.n[size_t(c)];
+    if (counted != n || res.n_single < 0 || res.n_single > n)
+      throw std::runtime_error("silhouette(): the result words' counts are out of range");
+  } else {
+    res.n_undefined = n;
+  }
+  if (per_row) {
+    res.rows = h_rows;
+    res.labels = h_labels;
+    res.neighbor = h_nb;
+    res.a = h_a;
+    res.b = h_b;
+    res.s = h_s;
+  }
+  return res;
+}
+
 KMResult KMEngine::process(int slot, bool want_labels) {
   TraceRange tr("twtml.km.batch");
   TWTML_HIP_CHECK(hipSetDevice(device_));
@@ -504,6 +625,45 @@ void bind_kmeans(py::module_& m) {
          py::arg("n") = 1, py::arg("largest") = true,
          "inference only: the n rows farthest from (largest) or closest to their centres, selected on the device: "
          "rows, values (squared distances), payload (labels), with the batch's cost, sizes and std")
+      .def("silhouette", [](KMEngine& e, int slot, bool apply_filter, int scaler_mode,
+                            std::optional<py::array_t<double, py::array::c_style | py::array::forcecast>> std,
+                            bool per_row) {
+        if (scaler_mode == kKmScalerGiven && (!std || std->size() != e.d()))
+          throw std::invalid_argument("silhouette(): the given scaler needs d stds");
+        KMSilResult r;
+        {
+          const double* sp = std ? std->data() : nullptr;
+          py::gil_scoped_release nogil;
+          r = e.silhouette(slot, apply_filter, scaler_mode, sp, per_row);
+        }
+        const KMScoreResult& b = r.batch;
+        py::dict out;
+        out["n_raw"] = b.n_raw;
+        out["n_scored"] = b.n_scored;
+        out["n"] = py::array_t<int64_t>(py::ssize_t(r.n.size()), r.n.data());
+        out["s_fix"] = py::array_t<int64_t>(py::ssize_t(r.s_fix.size()), r.s_fix.data());
+        out["n_single"] = r.n_single;
+        out["n_undefined"] = r.n_undefined;
+        out["nonempty"] = r.nonempty;
+        out["cost"] = b.cost;
+        out["sizes"] = py::array_t<int64_t>(py::ssize_t(b.sizes.size()), b.sizes.data());
+        out["std"] = py::array_t<double>(py::ssize_t(b.std.size()), b.std.data());
+        out["sil_ms"] = b.ms;
+        if (r.per_row) {   // copies owned by the caller (the engine's pinned block is reused)
+          const py::ssize_t n = r.rows ? py::ssize_t(b.n_scored) : 0;
+          out["rows"] = py::array_t<int64_t>(n, r.rows);
+          out["pred"] = py::array_t<int32_t>(n, r.labels);
+          out["neighbor"] = py::array_t<int32_t>(n, r.neighbor);
+          out["a"] = py::array_t<double>(n, r.a);
+          out["b"] = py::array_t<double>(n, r.b);
+          out["s"] = py::array_t<double>(n, r.s);
+        }
+        return out;
+      }, py::arg("slot"), py::arg("apply_filter") = true, py::arg("scaler_mode") = 0, py::arg("std") = py::none(),
+         py::arg("per_row") = false,
+         "inference only: the silhouette words of the batch in `slot` under the current model (n[k], s_fix[k] = "
+         "sum rint(s 2^36), n_single, n_undefined), with the batch's cost, sizes and std; per_row: also rows, "
+         "pred, neighbor, a, b, s")
       .def_static("cost_shape", [](int dp) {
         const KmCostShape sh = km_cost_shape(dp);
         return py::make_tuple(sh.lanes_per_row, sh.rows_per_wave, sh.rows_per_wg);

@@ -61,6 +61,20 @@ struct KMTopResult {
   TopResult top;
 };
 
+// silhouette(): the batch's integer words (models/silhouette.py), score()'s
+// batch-wide outputs, and with per_row the row arrays, which point into the
+// engine's pinned block: valid until the next silhouette().
+struct KMSilResult {
+  KMScoreResult batch;              // n_raw, n_scored, cost, sizes, std, ms (the whole pass); no per-row arrays
+  std::vector<int64_t> n, s_fix;    // [k] rows with a defined s | sum rint(s 2^36), per own cluster
+  int64_t n_single = 0, n_undefined = 0, nonempty = 0;
+  bool per_row = false;
+  const int64_t* rows = nullptr;    // [n_scored] raw row ids, ascending
+  const int32_t* labels = nullptr;  // [n_scored] own cluster (score()'s labels)
+  const int32_t* neighbor = nullptr;  // [n_scored] closest other cluster by mean distance, -1: none
+  const double *a = nullptr, *b = nullptr, *s = nullptr;
+};
+
 class KMEngine {
  public:
   KMEngine(int device, const KMConfig& cfg, std::shared_ptr<Comm> comm);
@@ -81,6 +95,16 @@ class KMEngine {
   // and the labels as payload.  Only the result block, the cost, the sizes and
   // the stds leave the device; no communicator is called.
   KMTopResult top(int slot, bool apply_filter, int scaler_mode, const double* std, int n, bool largest);
+  // The silhouette of the current model on the batch in `slot` (MLlib's
+  // ClusteringEvaluator, squared Euclidean; models/silhouette.py): score() up
+  // to and including the cost pass, the batch's own cluster means by the
+  // training path's exact integer sums, dev2 by the cost kernel against them,
+  // W by an order-independent fixed-point sum, then the neighbour pass of
+  // silhouette.hip.  Only 2k + 4 words, the cost, the sizes and the stds leave
+  // the device (per_row: also the row arrays).  score()'s guarantees: no
+  // communicator call, the model and its cached centres untouched; the
+  // scratch is allocated by the first call.
+  KMSilResult silhouette(int slot, bool apply_filter, int scaler_mode, const double* std, bool per_row);
   // Forget a submitted batch that will not be processed: waits for its H2D
   // (the staging buffer may then be rewritten); the copy stream keeps the
   // slot's next H2D in order behind it.
@@ -110,6 +134,7 @@ class KMEngine {
   void upload_factors(int mode, int64_t n, const double* given, std::vector<double>& std, hipStream_t s);
   void ensure_score();
   void ensure_top();
+  void ensure_sil();
   // What score() and top() share: filter .. the cost pass of the batch in
   // `slot`, ev0_ recorded first.  Returns the scored rows n (res.n_raw,
   // n_scored, sizes and std filled) and the device cost word; n == 0: nothing
@@ -150,6 +175,16 @@ class KMEngine {
   // top() only, allocated by its first call
   TopScratch top_sc_{};
   Pinned<int64_t> top_host_;           // result block of kTopNMax | cost | [k] sizes
+  // silhouette() only, allocated by its first call
+  double *sil_mean_ = nullptr, *sil_dev2_ = nullptr, *sil_part_ = nullptr;   // [k d] | [R] | [partials + 1]
+  double *sil_W_ = nullptr, *sil_V_ = nullptr;                               // [k] each
+  float *sil_mu32_ = nullptr, *sil_B_ = nullptr;                             // [k dp] | [k]
+  unsigned long long* sil_wacc_ = nullptr;                                   // [k] max bits | [k] fixed-point sums
+  int64_t *sil_hist_ = nullptr, *sil_sizes_ = nullptr, *sil_words_ = nullptr;   // [k + 1] | [k] | [2k + 4]
+  int32_t* sil_nb_ = nullptr;                                                // [R]
+  double *sil_a_ = nullptr, *sil_b_ = nullptr, *sil_s_ = nullptr;            // [R] each
+  // words | cost | [k] sizes | [R] rows | [R] a | [R] b | [R] s | [R] labels | [R] neighbor
+  Pinned<void> sil_host_;
 };
 
 void bind_kmeans(pybind11::module_& m);

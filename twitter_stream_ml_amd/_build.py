@@ -116,8 +116,11 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-f
 # eval.hip: no contraction (-ffp-contract=fast disregards the source's pragma):
 # every per-row term of the evaluation sums is a sequence of single IEEE
 # operations that the host reproduces bit for bit (models/metrics.py).
+# silhouette.hip: both -- MFMA accumulators read on the VALU after each tile,
+# and a, b, s are single IEEE operations (models/silhouette.py).
 HIP_FILE_FLAGS = {"kmeans.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-                  "eval.hip": ["-ffp-contract=off"]}
+                  "eval.hip": ["-ffp-contract=off"],
+                  "silhouette.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-ffp-contract=off"]}
 
 
 def build_hip(force: bool = False, verbose: bool = False) -> str:

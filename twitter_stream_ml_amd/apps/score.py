@@ -55,6 +55,21 @@ the labels, each row's squared distance to its centre and the batch's cost
                       combined with ``--predictOut`` and ``--evalOut`` (each runs its own
                       pass; give each its own directory).  ``--top`` without ``--topOut``
                       or N outside 1..4096 is a usage error (exit code 2).
+``--silhouetteOut DIR``  k-means models: the silhouette of every batch's retweets under the
+                      saved centres (``engine.silhouette_batch``: MLlib's
+                      ``ClusteringEvaluator``, squared Euclidean, ``models/silhouette.py``; on
+                      ``rocm[N]`` the neighbour pass of ``csrc/hip/silhouette.hip`` behind the
+                      scoring kernels, 2k + 4 words per batch back to the host).  Per batch
+                      one line of ``silhouette.jsonl`` -- seq, n_raw, n_scored, silhouette
+                      (null when fewer than two clusters are non-empty), n_single,
+                      n_undefined, clusters_used, cost, the accumulator, ms, sil_ms -- and at
+                      the end ``summary.json``: the merged accumulator, ``silhouette`` and
+                      ``cluster_silhouette``.  Every batch is measured against its own
+                      cluster means: the stream's figure is the row-weighted mean of its
+                      batches' silhouettes, not a silhouette over the whole stream.  May be
+                      combined with ``--predictOut``, ``--top`` and ``--scalerStd`` (each runs
+                      its own pass).  With a linear or logistic model it is a usage error
+                      (exit code 2).
 ``--scalerStd FILE``  k-means: ``.npy`` of d column stds, the frozen scaler
 ``--numBatches N``    stop after N batches
 
@@ -85,7 +100,7 @@ from ..utils.logging import setup_logging
 from ._common import exit_on_sigterm
 from .linear_regression import build_engine
 
-__all__ = ["main", "ScoreJob", "KMeansScoreJob", "EvalJob", "TopJob", "build_kmeans_scorer"]
+__all__ = ["main", "ScoreJob", "KMeansScoreJob", "EvalJob", "TopJob", "SilhouetteJob", "build_kmeans_scorer"]
 
 log = logging.getLogger("com.giorgioinf.twtml.spark.Score")
 APP_NAME = "twitter-stream-ml-score"
@@ -276,6 +291,49 @@ class TopJob:
             f.write("\n")
 
 
+class SilhouetteJob:
+    """Per-batch logic of ``--silhouetteOut``: the batch's silhouette
+    (``engine.silhouette_batch``) as one line of ``silhouette.jsonl``, the
+    merged accumulator with the stream's ``silhouette`` and
+    ``cluster_silhouette`` in ``summary.json`` at the end."""
+
+    def __init__(self, engine, k: int, out_dir: str, rank: int = 0, world: int = 1, **engine_kw):
+        from ..models.silhouette import SilhouetteAccumulator
+        self.engine = engine
+        self.kw = engine_kw
+        self.out_dir = out_dir
+        self.suffix = f"_r{rank}" if world > 1 else ""
+        self.batches = 0
+        self.total = SilhouetteAccumulator(k)
+        os.makedirs(out_dir, exist_ok=True)
+        self._jsonl = open(os.path.join(out_dir, f"silhouette{self.suffix}.jsonl"), "a", encoding="utf-8")
+
+    def on_batch(self, rdd, time_ms: int) -> None:
+        t0 = time.perf_counter()
+        res = self.engine.silhouette_batch(rdd.raw, apply_filter=True, **self.kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        acc = res["accumulator"]
+        self.total.merge(acc)
+        seq = self.batches
+        self.batches += 1
+        rec = {"seq": seq, "batch_time_ms": int(time_ms), "n_raw": int(res["n_raw"]), "n_scored": int(res["n_scored"]),
+               "silhouette": res["silhouette"], "n_single": acc.n_single, "n_undefined": acc.n_undefined,
+               "clusters_used": int(np.count_nonzero(res["sizes"])), "cost": float(res["cost"]),
+               "accumulator": acc.to_dict(), "ms": round(ms, 3), "sil_ms": round(float(res.get("sil_ms", 0.0)), 3)}
+        self._jsonl.write(json.dumps(rec) + "\n")
+        self._jsonl.flush()
+
+    def close(self) -> None:
+        if self._jsonl is None:
+            return
+        self._jsonl.close()
+        self._jsonl = None
+        summary = {"batches": self.batches, **self.total.summary()}
+        with open(os.path.join(self.out_dir, f"summary{self.suffix}.json"), "w", encoding="utf-8") as f:
+            json.dump(summary, f)
+            f.write("\n")
+
+
 def build_kmeans_scorer(conf, centers: np.ndarray, weights: np.ndarray, device: Optional[int]):
     """The engine that scores with a loaded k-means model: a DeviceKMeans on
     ``device`` (no communicator: every rank scores its own shard) or, with
@@ -326,7 +384,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 2
     if km is not None and conf.evalOut:
         print("twtml-score: --evalOut does not apply to a k-means model: its metric is the cost that "
-              "--predictOut already reports", file=sys.stderr)
+              "--predictOut already reports (--silhouetteOut measures the clustering itself)", file=sys.stderr)
+        return 2
+    if km is None and conf.silhouetteOut:
+        print("twtml-score: --silhouetteOut needs a k-means model; --evalOut evaluates a linear or logistic one",
+              file=sys.stderr)
         return 2
     if conf.top or conf.topOut or conf.topSmallest:
         from ..models.topn import TOPN_MAX
@@ -391,13 +453,18 @@ def main(argv: Optional[List[str]] = None) -> int:
         else:
             top = TopJob(engine, conf.top, not conf.topSmallest, conf.topOut, "logistic" if logistic else "linear",
                          rank, world, apply_filter=False)
-    score = (ev is None and top is None) or bool(conf.predictOut)
+    sil = None
+    if conf.silhouetteOut:
+        sil = SilhouetteJob(engine, int(w.shape[0]), conf.silhouetteOut, rank, world, scaler=scaler, **job._kw)
+    score = (ev is None and top is None and sil is None) or bool(conf.predictOut)
     if score:
         stream.foreachRDD(job.on_batch)
     if ev is not None:
         stream.foreachRDD(ev.on_batch)
     if top is not None:
         stream.foreachRDD(top.on_batch)
+    if sil is not None:
+        stream.foreachRDD(sil.on_batch)
     ssc.start()
     try:
         ssc.awaitTermination()
@@ -410,6 +477,10 @@ def main(argv: Optional[List[str]] = None) -> int:
             ev.close()
         if top is not None:
             top.close()
+        if sil is not None:
+            sil.close()
+    if sil is not None:
+        log.info("silhouette %s over %d batches", sil.total.silhouette, sil.batches)
     if ev is not None:
         log.info("evaluated %d batches", ev.batches)
     if top is not None:

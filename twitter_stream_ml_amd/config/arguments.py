@@ -20,7 +20,7 @@ short letters keep their meaning): ``--source``, ``--batchSize``,
 ``--resume``, ``--sourceRate``, ``--plotPoints``, ``--legacyNumTextFeatures``,
 ``--batchTimeout``, ``--checkReplicas``, ``--model``, ``--predictOut``,
 ``--scalerStd``, ``--evalOut``, ``--top``, ``--topSmallest`` (no value),
-``--topOut``.
+``--topOut``, ``--silhouetteOut``.
 The master accepts, besides Spark's ``local``, ``local[N]``, ``local[*]``
 (CPU plumbing engine, fp64), the device masters ``rocm``, ``rocm[N]``,
 ``rocm[*]`` and ``rocm:0,1,...`` (HIP engine, one process per GPU).
@@ -144,6 +144,7 @@ _EXT_FLAGS = {
     "--predictOut": ("predictOut", str),
     "--scalerStd": ("scalerStd", str),
     "--evalOut": ("evalOut", str),
+    "--silhouetteOut": ("silhouetteOut", str),
     "--top": ("top", int),
     "--topOut": ("topOut", str),
     # apps/logistic_regression.py (and apps/score.py with a logistic model)
@@ -210,6 +211,7 @@ class ConfArguments:
         self.predictOut = ""   # apps/score.py: directory of the per-batch prediction files
         self.scalerStd = ""    # apps/score.py, k-means models: .npy of d column stds (frozen scaler)
         self.evalOut = ""      # apps/score.py: directory of the held-out metrics (metrics.jsonl, summary.json)
+        self.silhouetteOut = ""   # apps/score.py, k-means models: directory of silhouette.jsonl and summary.json
         self.top = 0           # apps/score.py: select the N best rows of every batch (0: off)
         self.topSmallest = False   # ... the lowest values instead of the highest
         self.topOut = ""       # apps/score.py: directory of top.jsonl and summary.json
@@ -264,6 +266,10 @@ Usage: twtml-spark [options]
                                                   batch (k-means: the N farthest from their centres), selected on
                                                   the device; --topSmallest: the lowest.  top.jsonl per batch,
                                                   summary.json: the best N of the stream
+  --silhouetteOut <dir>                           scoring driver, k-means models: the silhouette of every batch
+                                                  (MLlib's ClusteringEvaluator, squared Euclidean) against the
+                                                  batch's own cluster means: silhouette.jsonl per batch,
+                                                  summary.json: the row-weighted mean over the stream
   --scalerStd <file.npy>                          scoring driver, k-means models: the d column stds of a
                                                   frozen scaler (default: a StandardScaler fitted per batch)
   --labelThreshold <n>  --threshold <p>           logistic driver (apps.logistic_regression / twtml-logistic):

@@ -267,6 +267,40 @@ class CpuKMeans:
                 "dist2": dist2, "cost": float(dist2.sum()), "sizes": np.bincount(pred, minlength=k).astype(np.int64),
                 "std": std, "score_ms": ms, "wall_ms": ms}
 
+    def silhouette_batch(self, raw: RawBatch, text_dims: int, apply_filter: bool = True, scaler="batch",
+                         per_row: bool = False) -> Dict[str, object]:
+        """The silhouette of the current model on one raw batch (MLlib's
+        ``ClusteringEvaluator``, squared Euclidean), the contract of
+        ``DeviceKMeans.silhouette_batch``: ``models/silhouette.py`` applied in
+        fp64 to this engine's own ``predict_batch`` labels.  ``silhouette``
+        (None when fewer than two clusters are non-empty), ``accumulator``
+        (a ``SilhouetteAccumulator`` of this batch), ``sizes``, ``cost``,
+        ``std``, ``n_raw``, ``n_scored``; ``per_row``: also ``rows``, ``pred``,
+        ``neighbor`` (int32, -1 where undefined), ``a``, ``b``, ``s``.  Every
+        batch is measured against its own cluster means; the model is left as
+        it is."""
+        from .silhouette import SilhouetteAccumulator, batch_silhouette, empty_silhouette
+        t0 = time.perf_counter()
+        k = self.state.centers.shape[0]
+        res = self.predict_batch(raw, text_dims, apply_filter=apply_filter, scaler=scaler)
+        n = int(res["n_scored"])
+        if n == 0:
+            return empty_silhouette(raw.n, k, res["std"], per_row)
+        X, rows = kmeans_features(raw, text_dims, apply_filter=apply_filter)
+        Xs = X if res["std"] is None else standard_scaler_transform(X, res["std"])
+        b = batch_silhouette(Xs, res["pred"], k)
+        acc = SilhouetteAccumulator(k)
+        if b["defined"]:
+            acc.add_rows(res["pred"], b["s"])
+        else:
+            acc.add_undefined(n)
+        ms = (time.perf_counter() - t0) * 1e3
+        out = {"n_raw": int(raw.n), "n_scored": n, "silhouette": acc.silhouette, "accumulator": acc,
+               "sizes": res["sizes"], "cost": res["cost"], "std": res["std"], "sil_ms": ms, "wall_ms": ms}
+        if per_row:
+            out.update(rows=rows, pred=res["pred"], neighbor=b["neighbor"], a=b["a"], b=b["b"], s=b["s"])
+        return out
+
     def top_batch(self, raw: RawBatch, n: int, text_dims: int, largest: bool = True, apply_filter: bool = True,
                   scaler="batch") -> Dict[str, object]:
         """The n rows farthest from their centres (``largest``: the batch's

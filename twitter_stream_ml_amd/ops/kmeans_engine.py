@@ -221,6 +221,49 @@ class DeviceKMeans:
                 "n_raw": int(r["n_raw"]), "n_scored": int(r["n_scored"]), "top_ms": float(r["top_ms"]),
                 "wall_ms": (time.perf_counter() - t0) * 1e3}
 
+    # ---- silhouette (KMEngine::silhouette, csrc/hip/silhouette.hip) --------
+    def silhouette_batch(self, raw: RawBatch, apply_filter: bool = True, scaler="batch",
+                         per_row: bool = False) -> Dict[str, object]:
+        """The silhouette of the current model on one raw micro-batch (MLlib's
+        ``ClusteringEvaluator``, squared Euclidean; the contract of
+        ``models/silhouette.py``), computed on the device: ``predict_batch``'s
+        passes, the batch's own cluster means, then the neighbour pass.
+        ``silhouette`` (None when fewer than two clusters are non-empty),
+        ``accumulator`` (this batch's ``SilhouetteAccumulator``: integers that
+        merge exactly across batches and ranks), ``sizes``, ``cost``, ``std``,
+        ``n_raw``, ``n_scored``, ``sil_ms`` (device time) and ``wall_ms``; only
+        2k + 4 words, the cost, the sizes and the stds leave the device.
+        ``per_row``: also ``rows``, ``pred``, ``neighbor`` (int32, -1 where
+        undefined), ``a``, ``b``, ``s`` (fp64).  Every batch is measured against
+        its own cluster means, so a stream's merged figure is the row-weighted
+        mean of its batches' silhouettes.  Arguments and guarantees are
+        ``predict_batch``'s: no collective, the model untouched.  A batch may
+        hold up to 2^22 scored rows (the range of the fixed-point sum behind
+        ``W``); a larger one is refused."""
+        from ..models.silhouette import SilhouetteAccumulator, empty_silhouette
+        mode, std = scaler_mode(scaler, self.dim, bool(self.cfg.scale))
+        if raw.n == 0:                # nothing is staged or launched
+            return empty_silhouette(0, self.cfg.k, std, per_row)
+        t0 = time.perf_counter()
+        slot = self._pipe.free_slot()
+        try:
+            self.submit(self._stage(slot, raw), slot)
+            r = self._eng.silhouette(int(slot), bool(apply_filter), mode, std, bool(per_row))
+        finally:
+            self._pipe.score_done(slot)
+        n = int(r["n_scored"])
+        acc = SilhouetteAccumulator(self.cfg.k)
+        if n:
+            acc.add_words(r["n"], r["s_fix"], int(r["n_single"]), int(r["n_undefined"]))
+        out = {"n_raw": int(r["n_raw"]), "n_scored": n, "silhouette": acc.silhouette, "accumulator": acc,
+               "sizes": np.asarray(r["sizes"]), "cost": float(r["cost"]),
+               "std": std.copy() if std is not None else (np.asarray(r["std"]) if len(r["std"]) else None),
+               "sil_ms": float(r["sil_ms"]), "wall_ms": (time.perf_counter() - t0) * 1e3}
+        if per_row:
+            for key in ("rows", "pred", "neighbor", "a", "b", "s"):
+                out[key] = np.asarray(r[key])
+        return out
+
     @property
     def h2d_bytes(self) -> int:
         """Host-to-device bytes submitted so far (every copy of every batch)."""
