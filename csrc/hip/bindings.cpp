@@ -68,6 +68,34 @@ py::dict twtml::top_dict(const TopResult& r) {
   return d;
 }
 
+// A per-cluster selection's result as arrays owned by the caller: counts[k],
+// rows[k, m] (-1 in unused entries), values[k, m] (the original bits).
+py::dict twtml::exemplar_dict(const KMExemplarResult& r) {
+  const py::ssize_t k = r.k, m = r.m;
+  py::array_t<int64_t> counts(k);
+  py::array_t<int64_t> rows({k, m});
+  py::array_t<double> values({k, m});
+  if (r.counts) {
+    std::memcpy(counts.mutable_data(), r.counts, sizeof(int64_t) * size_t(k));
+    std::memcpy(rows.mutable_data(), r.rows, sizeof(int64_t) * size_t(k) * size_t(m));
+    std::memcpy(values.mutable_data(), r.bits, sizeof(double) * size_t(k) * size_t(m));
+  } else {   // nothing was scored
+    std::fill_n(counts.mutable_data(), k, int64_t(0));
+    std::fill_n(rows.mutable_data(), k * m, int64_t(-1));
+    std::fill_n(values.mutable_data(), k * m, 0.0);
+  }
+  py::dict d;
+  d["n_raw"] = r.batch.n_raw;
+  d["n_scored"] = r.batch.n_scored;
+  d["n_nan"] = r.n_nan;
+  d["counts"] = counts;
+  d["rows"] = rows;
+  d["values"] = values;
+  d["ex_ms"] = r.ex_ms;
+  d["sel_ms"] = r.sel_ms;
+  return d;
+}
+
 static py::dict result_dict(BatchResult& r) {
   py::dict d;
   d["n_raw"] = r.n_raw;

@@ -283,6 +283,139 @@ KMTopResult KMEngine::top(int slot, bool apply_filter, int scaler_mode, const do
   return res;
 }
 
+// ---------------------------------------------------------------------------
+// Exemplars (exemplars.hip): score()'s pass, then one top-m per cluster.
+// ---------------------------------------------------------------------------
+static void check_ex(const char* who, int64_t k, int m) {
+  if (m < 1 || m > kExMaxM || k < 1 || k * m > kExMaxCells)
+    throw std::invalid_argument(std::string(who) + ": m must be in [1, " + std::to_string(kExMaxM) +
+                                "] and k * m at most " + std::to_string(kExMaxCells) + "; use score() for every row");
+}
+
+void KMEngine::ensure_ex(int64_t kcap, size_t out_words) {
+  if (ex_sc_.out && ex_sc_.kcap >= kcap && ex_sc_.out_words >= out_words) return;
+  kcap = std::max(kcap, ex_sc_.kcap);   // debug_cluster_select() with a larger k: never smaller than before
+  out_words = std::max(out_words, ex_sc_.out_words);
+  if (!ex_ev_) ex_ev_ = Event(hipEventDefault);
+  const size_t host_words = out_words + 1 + size_t(cfg_.k);
+  if (host_words > ex_host_words_) {
+    ex_host_.alloc(sizeof(int64_t) * host_words, hipHostMallocDefault);
+    ex_host_words_ = host_words;
+  }
+  ex_sc_ = ExScratch{};
+  arena_.grow(ex_buf_, ex_scratch_words(cfg_.max_rows, kcap, out_words), compute_);
+  ex_sc_ = ex_scratch_carve(ex_buf_, cfg_.max_rows, kcap, out_words);
+}
+
+KMExemplarResult KMEngine::ex_result(int k, int m, const double* cost) {
+  hipStream_t s = compute_;
+  const size_t words = ex_out_words(k, m);
+  int64_t* h = ex_host_.get();
+  int64_t* h_cost = h + words;
+  int64_t* h_sizes = h_cost + 1;
+  TWTML_HIP_CHECK(hipMemcpyAsync(h, ex_sc_.out, sizeof(int64_t) * words, hipMemcpyDeviceToHost, s));
+  if (cost) {
+    TWTML_HIP_CHECK(hipMemcpyAsync(h_cost, cost, sizeof(double), hipMemcpyDeviceToHost, s));
+    TWTML_HIP_CHECK(hipMemcpyAsync(h_sizes, lhist_, sizeof(int64_t) * size_t(cfg_.k), hipMemcpyDeviceToHost, s));
+  }
+  TWTML_HIP_CHECK(hipStreamSynchronize(s));
+  KMExemplarResult res;
+  res.k = k;
+  res.m = m;
+  res.n_nan = h[kExNNan];
+  res.batch.n_scored = h[kExCnt];
+  res.counts = h + kExHead;
+  res.bits = res.counts + k;
+  res.rows = res.bits + size_t(k) * size_t(m);
+  if (res.n_nan < 0 || res.n_nan > res.batch.n_scored)
+    throw std::runtime_error("exemplars(): the result block's counts are out of range");
+  if (cost) {
+    std::memcpy(&res.batch.cost, h_cost, sizeof(double));
+    res.batch.sizes.assign(h_sizes, h_sizes + cfg_.k);
+  }
+  return res;
+}
+
+KMExemplarResult KMEngine::exemplars(int slot, bool apply_filter, int scaler_mode, const double* std, int m,
+                                     bool largest) {
+  check_ex("exemplars()", cfg_.k, m);
+  TraceRange tr("twtml.km.exemplars");
+  KMScoreResult batch;
+  double* cost = nullptr;
+  const int64_t ns = score_kernels("exemplars()", slot, apply_filter, scaler_mode, std, batch, &cost);
+  if (ns == 0) {
+    KMExemplarResult res;
+    res.batch = std::move(batch);
+    res.k = cfg_.k;
+    res.m = m;
+    res.ex_ms = res.batch.ms;
+    return res;
+  }
+  const int64_t m_most = std::min<int64_t>(kExMaxM, kExMaxCells / cfg_.k);
+  ensure_ex(cfg_.k, ex_out_words(cfg_.k, int(m_most)));
+  hipStream_t s = compute_;
+  TWTML_HIP_CHECK(hipEventRecord(ex_ev_, s));
+  launch_cluster_select(dist2_, labels_, prep_.kept, prep_.counters, ns, cfg_.k, m, largest, lhist_, ex_sc_, s);
+  TWTML_HIP_CHECK(hipEventRecord(ev1_, s));
+  KMExemplarResult res = ex_result(cfg_.k, m, cost);
+  if (res.batch.n_scored != ns) throw std::runtime_error("exemplars(): the result block's row count is out of range");
+  res.batch.n_raw = batch.n_raw;
+  res.batch.std = std::move(batch.std);
+  TWTML_HIP_CHECK(hipEventElapsedTime(&res.batch.ms, ev0_, ev1_));
+  TWTML_HIP_CHECK(hipEventElapsedTime(&res.sel_ms, ex_ev_, ev1_));
+  res.ex_ms = res.batch.ms;
+  return res;
+}
+
+KMExemplarResult KMEngine::debug_cluster_select(const double* values, const int32_t* labels, const int64_t* rows,
+                                                int64_t count, int k, int m, bool largest) {
+  check_ex("debug_cluster_select()", k, m);
+  if (count < 0 || count > cfg_.max_rows)
+    throw std::invalid_argument("debug_cluster_select(): more values than max_rows");
+  TWTML_HIP_CHECK(hipSetDevice(device_));
+  // the buffers of a scoring pass stand in for its outputs: dist2_ / labels_ /
+  // the kept row ids / the row counter on the device, score()'s pinned block
+  // as the staging of the caller's arrays (what the last score() left there is
+  // overwritten); only the sizes of the caller's k are the entry's own
+  ensure_score();
+  ensure_ex(k, ex_out_words(k, m));
+  if (k > ex_dbg_k_) {
+    arena_.grow(ex_dbg_sizes_, size_t(k), compute_);
+    ex_dbg_k_ = k;
+  }
+  hipStream_t s = compute_;
+  const size_t R = size_t(cfg_.max_rows), un = size_t(count);
+  auto* h_rows = static_cast<int64_t*>(score_host_.get());
+  auto* h_vals = reinterpret_cast<double*>(h_rows + R);
+  auto* h_labels = reinterpret_cast<int32_t*>(reinterpret_cast<int64_t*>(h_vals + R + 1) + cfg_.k);
+  int64_t* d_sizes = ex_dbg_sizes_;
+  double* dv = dist2_;
+  int64_t* dr = prep_.kept;
+  int32_t* dl = labels_;
+  std::memcpy(host_out_ + 1, &count, sizeof(int64_t));
+  TWTML_HIP_CHECK(hipMemsetAsync(prep_.counters, 0, 8 * sizeof(int64_t), s));
+  TWTML_HIP_CHECK(hipMemcpyAsync(prep_.counters, host_out_ + 1, sizeof(int64_t), hipMemcpyHostToDevice, s));
+  if (count > 0) {
+    std::memcpy(h_vals, values, sizeof(double) * un);
+    std::memcpy(h_labels, labels, sizeof(int32_t) * un);
+    TWTML_HIP_CHECK(hipMemcpyAsync(dv, h_vals, sizeof(double) * un, hipMemcpyHostToDevice, s));
+    TWTML_HIP_CHECK(hipMemcpyAsync(dl, h_labels, sizeof(int32_t) * un, hipMemcpyHostToDevice, s));
+    if (rows) {
+      std::memcpy(h_rows, rows, sizeof(int64_t) * un);
+      TWTML_HIP_CHECK(hipMemcpyAsync(dr, h_rows, sizeof(int64_t) * un, hipMemcpyHostToDevice, s));
+    }
+  }
+  launch_cluster_sizes(dl, prep_.counters, count, k, d_sizes, s);
+  TWTML_HIP_CHECK(hipEventRecord(ex_ev_, s));
+  launch_cluster_select(dv, dl, rows ? dr : nullptr, prep_.counters, count, k, m, largest, d_sizes, ex_sc_, s);
+  TWTML_HIP_CHECK(hipEventRecord(ev1_, s));
+  KMExemplarResult res = ex_result(k, m, nullptr);
+  res.batch.n_raw = count;
+  TWTML_HIP_CHECK(hipEventElapsedTime(&res.sel_ms, ex_ev_, ev1_));
+  res.ex_ms = res.sel_ms;
+  return res;
+}
+
 void KMEngine::ensure_sil() {
   if (sil_mean_) return;
   const size_t R = size_t(cfg_.max_rows), k = size_t(cfg_.k), d = size_t(d_);
@@ -625,6 +758,56 @@ void bind_kmeans(py::module_& m) {
          py::arg("n") = 1, py::arg("largest") = true,
          "inference only: the n rows farthest from (largest) or closest to their centres, selected on the device: "
          "rows, values (squared distances), payload (labels), with the batch's cost, sizes and std")
+      .def("exemplars", [](KMEngine& e, int slot, bool apply_filter, int scaler_mode,
+                           std::optional<py::array_t<double, py::array::c_style | py::array::forcecast>> std, int m,
+                           bool largest) {
+        if (scaler_mode == kKmScalerGiven && (!std || std->size() != e.d()))
+          throw std::invalid_argument("exemplars(): the given scaler needs d stds");
+        KMExemplarResult r;
+        {
+          const double* sp = std ? std->data() : nullptr;
+          py::gil_scoped_release nogil;
+          r = e.exemplars(slot, apply_filter, scaler_mode, sp, m, largest);
+        }
+        py::dict out = exemplar_dict(r);
+        out["cost"] = r.batch.cost;
+        out["sizes"] = py::array_t<int64_t>(py::ssize_t(r.batch.sizes.size()), r.batch.sizes.data());
+        out["std"] = py::array_t<double>(py::ssize_t(r.batch.std.size()), r.batch.std.data());
+        return out;
+      }, py::arg("slot"), py::arg("apply_filter") = true, py::arg("scaler_mode") = 0, py::arg("std") = py::none(),
+         py::arg("m") = 1, py::arg("largest") = false,
+         "inference only: per cluster, the m rows closest to (largest: farthest from) their centre, selected on the "
+         "device: counts[k], rows[k, m], values[k, m] (squared distances), n_nan, with the batch's cost, sizes and std")
+      .def("debug_cluster_select",
+           [](KMEngine& e, py::array_t<double, py::array::c_style | py::array::forcecast> values,
+              py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels,
+              std::optional<py::array_t<int64_t, py::array::c_style | py::array::forcecast>> rows, int k, int m,
+              bool largest) {
+             if (values.ndim() != 1 || labels.ndim() != 1 || labels.size() != values.size() ||
+                 (rows && (rows->ndim() != 1 || rows->size() != values.size())))
+               throw std::invalid_argument(
+                   "debug_cluster_select(): values, labels and rows are 1-d arrays of one length");
+             for (py::ssize_t i = 0; i < labels.size(); ++i)
+               if (labels.data()[i] < 0 || labels.data()[i] >= k)
+                 throw std::invalid_argument("debug_cluster_select(): labels must lie in [0, k)");
+             KMExemplarResult r;
+             {
+               const double* v = values.data();
+               const int32_t* l = labels.data();
+               const int64_t* rp = rows ? rows->data() : nullptr;
+               const int64_t count = values.size();
+               py::gil_scoped_release nogil;
+               r = e.debug_cluster_select(v, l, rp, count, k, m, largest);
+             }
+             py::dict d = exemplar_dict(r);
+             d["tile"] = kExTile;
+             d["chunk"] = kExChunk;
+             return d;
+           },
+           py::arg("values"), py::arg("labels"), py::arg("rows") = py::none(), py::arg("k") = 1, py::arg("m") = 1,
+           py::arg("largest") = false,
+           "debug/test: the per-cluster selection kernels alone over host arrays (at most max_rows; k is the "
+           "caller's); also the tile and chunk constants of the two passes")
       .def("silhouette", [](KMEngine& e, int slot, bool apply_filter, int scaler_mode,
                             std::optional<py::array_t<double, py::array::c_style | py::array::forcecast>> std,
                             bool per_row) {

@@ -9,6 +9,7 @@
 #include "comm.h"
 #include "common.h"
 #include "engine.h"
+#include "exemplars.h"
 #include "kernels.h"
 #include "owned.h"
 
@@ -75,6 +76,21 @@ struct KMSilResult {
   const double *a = nullptr, *b = nullptr, *s = nullptr;
 };
 
+// exemplars(): score()'s batch-wide outputs and, per cluster, the m rows
+// nearest their centre (largest: farthest), models/exemplars.py.  The arrays
+// point into the engine's pinned block: valid until the next exemplars() or
+// debug_cluster_select().
+struct KMExemplarResult {
+  KMScoreResult batch;              // n_raw, n_scored, cost, sizes, std, ms (through the selection); no per-row arrays
+  int32_t k = 0, m = 0;
+  int64_t n_nan = 0;
+  const int64_t* counts = nullptr;  // [k] entries selected
+  const int64_t* bits = nullptr;    // [k][m] value bits, best first; 0 beyond counts[c]
+  const int64_t* rows = nullptr;    // [k][m] raw row ids; -1 beyond counts[c]
+  float ex_ms = 0.f;                // device time (events): exemplars() the whole pass, debug: the selection
+  float sel_ms = 0.f;               // ... of the selection kernels alone
+};
+
 class KMEngine {
  public:
   KMEngine(int device, const KMConfig& cfg, std::shared_ptr<Comm> comm);
@@ -105,6 +121,21 @@ class KMEngine {
   // communicator call, the model and its cached centres untouched; the
   // scratch is allocated by the first call.
   KMSilResult silhouette(int slot, bool apply_filter, int scaler_mode, const double* std, bool per_row);
+  // Per cluster, the m rows (1 <= m <= kExMaxM, k m <= kExMaxCells) nearest
+  // their centre (largest: farthest from it): score() up to and including the
+  // cost pass, then the segmented selection of exemplars.hip over the squared
+  // distances, the labels and the kept row ids, with the cost pass's cluster
+  // sizes as the candidates' exact capacity.  Only the result block, the cost,
+  // the sizes and the stds leave the device.  score()'s guarantees: no
+  // communicator call; the model, its cached centres, the other raw slots and
+  // a pending update untouched; the scratch is allocated by the first call.
+  KMExemplarResult exemplars(int slot, bool apply_filter, int scaler_mode, const double* std, int m, bool largest);
+  // Debug/test: the selection kernels alone on the caller's arrays (count <=
+  // max_rows; rows may be null); k is independent of the model's.  The arrays
+  // take the place of a scoring pass's outputs, so debug_labels() and the
+  // pinned arrays of the last score() are overwritten.
+  KMExemplarResult debug_cluster_select(const double* values, const int32_t* labels, const int64_t* rows,
+                                        int64_t count, int k, int m, bool largest);
   // Forget a submitted batch that will not be processed: waits for its H2D
   // (the staging buffer may then be rewritten); the copy stream keeps the
   // slot's next H2D in order behind it.
@@ -135,6 +166,10 @@ class KMEngine {
   void ensure_score();
   void ensure_top();
   void ensure_sil();
+  void ensure_ex(int64_t kcap, size_t out_words);
+  // The result block of a selection of (k, m) and, with `cost`, the cost and
+  // the engine's sizes, copied to ex_host_ (syncs the compute stream).
+  KMExemplarResult ex_result(int k, int m, const double* cost);
   // What score() and top() share: filter .. the cost pass of the batch in
   // `slot`, ev0_ recorded first.  Returns the scored rows n (res.n_raw,
   // n_scored, sizes and std filled) and the device cost word; n == 0: nothing
@@ -175,6 +210,15 @@ class KMEngine {
   // top() only, allocated by its first call
   TopScratch top_sc_{};
   Pinned<int64_t> top_host_;           // result block of kTopNMax | cost | [k] sizes
+  // exemplars() only, allocated by its first call (debug_cluster_select():
+  // regrown for a larger k of the caller's)
+  ExScratch ex_sc_{};
+  int64_t* ex_buf_ = nullptr;          // the scratch ex_sc_ is carved from
+  int64_t* ex_dbg_sizes_ = nullptr;    // debug_cluster_select(): [ex_dbg_k_] sizes of the caller's labels
+  int ex_dbg_k_ = 0;
+  Pinned<int64_t> ex_host_;            // result block | cost | [k] sizes
+  size_t ex_host_words_ = 0;
+  Event ex_ev_;                        // before the selection
   // silhouette() only, allocated by its first call
   double *sil_mean_ = nullptr, *sil_dev2_ = nullptr, *sil_part_ = nullptr;   // [k d] | [R] | [partials + 1]
   double *sil_W_ = nullptr, *sil_V_ = nullptr;                               // [k] each
@@ -190,5 +234,6 @@ class KMEngine {
 void bind_kmeans(pybind11::module_& m);
 // A selection's result as a dict of arrays owned by the caller (bindings.cpp).
 pybind11::dict top_dict(const TopResult& r);
+pybind11::dict exemplar_dict(const KMExemplarResult& r);
 
 }  // namespace twtml

@@ -70,6 +70,26 @@ the labels, each row's squared distance to its centre and the batch's cost
                       combined with ``--predictOut``, ``--top`` and ``--scalerStd`` (each runs
                       its own pass).  With a linear or logistic model it is a usage error
                       (exit code 2).
+``--exemplars M``     with ``--exemplarsOut DIR``, k-means models: what each cluster is about --
+                      per cluster, the M (1..64, k M <= 2^18) retweets of every batch nearest
+                      its centre (``engine.exemplars_batch``, ``models/exemplars.py``; on
+                      ``rocm[N]`` the segmented selection of ``csrc/hip/exemplars.hip`` behind
+                      the scoring kernels: k x M entries come back, not the labels and
+                      distances of every row); ``--exemplarsFarthest``: each cluster's own
+                      outliers.  Per batch one line of ``exemplars.jsonl`` -- seq, batch time,
+                      n_raw, n_scored, n_nan, clusters_used, cost, ms, ex_ms and ``clusters``:
+                      for each non-empty cluster ``label``, ``size`` and ``entries``, best
+                      first, ties by row: ``row``, ``dist2``, the row's ``retweetCount`` and
+                      ``text`` -- and at the end ``summary.json``: the best M per cluster of
+                      the stream (``models/exemplars.ExemplarMerger``; entries carry ``seq``)
+                      and ``"scaler"``: ``"batch"``, ``"given"`` or ``"none"``.  Distances of
+                      different batches are on one scale only with ``--scalerStd`` or no
+                      scaler: under the per-batch scaler the summary merges distances
+                      measured in each batch's own units.  May be combined with
+                      ``--predictOut``, ``--top``, ``--silhouetteOut`` and ``--scalerStd``
+                      (each runs its own pass).  ``--exemplars`` without ``--exemplarsOut`` or
+                      the reverse, M outside 1..64, k M > 2^18 or a linear or logistic model
+                      is a usage error (exit code 2).
 ``--scalerStd FILE``  k-means: ``.npy`` of d column stds, the frozen scaler
 ``--numBatches N``    stop after N batches
 
@@ -77,7 +97,8 @@ With more than one rank (``rocm[N>1]``, one process per GPU) every rank
 scores its own shard of the stream and writes its own files, suffixed
 ``_r<rank>``; scoring needs no collective.  The ranks' ``metrics_r<rank>.jsonl``
 accumulators combine exactly with ``EvalAccumulator.from_dict`` + ``merge``,
-and the lines of their ``top_r<rank>.jsonl`` with ``TopNMerger.add``.
+the lines of their ``top_r<rank>.jsonl`` with ``TopNMerger.add`` and those of
+their ``exemplars_r<rank>.jsonl`` with ``ExemplarMerger.add``.
 """
 from __future__ import annotations
 
@@ -100,7 +121,8 @@ from ..utils.logging import setup_logging
 from ._common import exit_on_sigterm
 from .linear_regression import build_engine
 
-__all__ = ["main", "ScoreJob", "KMeansScoreJob", "EvalJob", "TopJob", "SilhouetteJob", "build_kmeans_scorer"]
+__all__ = ["main", "ScoreJob", "KMeansScoreJob", "EvalJob", "TopJob", "SilhouetteJob", "ExemplarsJob",
+           "build_kmeans_scorer"]
 
 log = logging.getLogger("com.giorgioinf.twtml.spark.Score")
 APP_NAME = "twitter-stream-ml-score"
@@ -334,6 +356,75 @@ class SilhouetteJob:
             f.write("\n")
 
 
+class ExemplarsJob:
+    """Per-batch logic of ``--exemplars M``: per cluster the batch's M rows
+    nearest the centre (``engine.exemplars_batch``; ``largest``: the farthest)
+    as one line of ``exemplars.jsonl``, the best M per cluster of the whole
+    stream (``models/exemplars.ExemplarMerger``) in ``summary.json`` at the end.
+    The scaler the engine is called with is recorded there by name (an array of
+    stds: ``"given"``; else ``"batch"`` or ``"none"`` as passed; the driver
+    passes the first two): distances of different batches are on one scale only
+    with a given scaler or none -- under the per-batch scaler the summary merges
+    distances measured in each batch's own units."""
+
+    def __init__(self, engine, k: int, m: int, largest: bool, out_dir: str, rank: int = 0, world: int = 1,
+                 **engine_kw):
+        from ..models.exemplars import ExemplarMerger
+        self.engine = engine
+        self.k, self.m, self.largest = int(k), int(m), bool(largest)
+        scaler = engine_kw.get("scaler", "batch")
+        self.scaler_name = scaler if isinstance(scaler, str) else "given"
+        self.kw = engine_kw
+        self.out_dir = out_dir
+        self.suffix = f"_r{rank}" if world > 1 else ""
+        self.batches = 0
+        self.merger = ExemplarMerger(self.k, self.m, self.largest)
+        os.makedirs(out_dir, exist_ok=True)
+        self._jsonl = open(os.path.join(out_dir, f"exemplars{self.suffix}.jsonl"), "a", encoding="utf-8")
+
+    def _clusters(self, raw, res) -> List[dict]:
+        from ..records.batch import RETWEET_COUNT
+        out = []
+        for c in np.flatnonzero(np.asarray(res["sizes"]) > 0):
+            n = int(res["counts"][c])
+            entries = [{"row": int(r), "dist2": float(v), "retweetCount": int(raw.scalars[RETWEET_COUNT][int(r)]),
+                        "text": raw.text_of(int(r))} for r, v in zip(res["rows"][c, :n], res["values"][c, :n])]
+            out.append({"label": int(c), "size": int(res["sizes"][c]), "entries": entries})
+        return out
+
+    def on_batch(self, rdd, time_ms: int) -> None:
+        raw = rdd.raw
+        t0 = time.perf_counter()
+        res = self.engine.exemplars_batch(raw, self.m, largest=self.largest, **self.kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        clusters = self._clusters(raw, res)
+        seq = self.batches
+        self.batches += 1
+        extras = {(c["label"], e["row"]): {"retweetCount": e["retweetCount"], "text": e["text"]}
+                  for c in clusters for e in c["entries"]}
+        self.merger.add(seq, res["counts"], res["rows"], res["values"], extras, int(res["n_nan"]))
+        rec = {"seq": seq, "batch_time_ms": int(time_ms), "n_raw": int(res["n_raw"]), "n_scored": int(res["n_scored"]),
+               "n_nan": int(res["n_nan"]), "clusters_used": int(np.count_nonzero(res["sizes"])),
+               "cost": float(res["cost"]), "ms": round(ms, 3), "ex_ms": round(float(res.get("ex_ms", 0.0)), 3),
+               "clusters": clusters}
+        self._jsonl.write(json.dumps(rec) + "\n")
+        self._jsonl.flush()
+
+    def close(self) -> None:
+        if self._jsonl is None:
+            return
+        self._jsonl.close()
+        self._jsonl = None
+        clusters = [{"label": c["label"], "entries": [{**{k: v for k, v in e.items() if k != "value"},
+                                                       "dist2": e["value"]} for e in c["entries"]]}
+                    for c in self.merger.result()]
+        summary = {"batches": self.batches, "k": self.k, "m": self.m, "largest": self.largest,
+                   "scaler": self.scaler_name, "n_nan": self.merger.n_nan, "clusters": clusters}
+        with open(os.path.join(self.out_dir, f"summary{self.suffix}.json"), "w", encoding="utf-8") as f:
+            json.dump(summary, f)
+            f.write("\n")
+
+
 def build_kmeans_scorer(conf, centers: np.ndarray, weights: np.ndarray, device: Optional[int]):
     """The engine that scores with a loaded k-means model: a DeviceKMeans on
     ``device`` (no communicator: every rank scores its own shard) or, with
@@ -396,6 +487,23 @@ def main(argv: Optional[List[str]] = None) -> int:
             print(f"twtml-score: --top N needs N in 1..{TOPN_MAX} and --topOut <dir> (got --top {conf.top}, "
                   f"--topOut {conf.topOut!r}); --predictOut writes every row", file=sys.stderr)
             return 2
+    if conf.exemplars or conf.exemplarsOut or conf.exemplarsFarthest:
+        from ..models.exemplars import EXEMPLARS_MAX, check_m
+        if km is None:
+            print("twtml-score: --exemplars needs a k-means model; --top selects the best rows of a linear or "
+                  "logistic one", file=sys.stderr)
+            return 2
+        if not conf.exemplarsOut or not 1 <= conf.exemplars <= EXEMPLARS_MAX:
+            print(f"twtml-score: --exemplars M needs M in 1..{EXEMPLARS_MAX} and --exemplarsOut <dir> (got --exemplars "
+                  f"{conf.exemplars}, --exemplarsOut {conf.exemplarsOut!r}); --predictOut writes every row",
+                  file=sys.stderr)
+            return 2
+        try:
+            check_m(int(w.shape[0]), conf.exemplars)
+        except ValueError as e:
+            print(f"twtml-score: --exemplars {conf.exemplars} with the {w.shape[0]} centres of {conf.model}: {e}",
+                  file=sys.stderr)
+            return 2
     scaler = "batch"
     if km is not None:
         text_dims = (w.shape[1] if w.ndim == 2 else 0) - 2
@@ -456,7 +564,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     sil = None
     if conf.silhouetteOut:
         sil = SilhouetteJob(engine, int(w.shape[0]), conf.silhouetteOut, rank, world, scaler=scaler, **job._kw)
-    score = (ev is None and top is None and sil is None) or bool(conf.predictOut)
+    ex = None
+    if conf.exemplars:
+        ex = ExemplarsJob(engine, int(w.shape[0]), conf.exemplars, conf.exemplarsFarthest, conf.exemplarsOut,
+                          rank, world, apply_filter=True, scaler=scaler, **job._kw)
+    score = (ev is None and top is None and sil is None and ex is None) or bool(conf.predictOut)
     if score:
         stream.foreachRDD(job.on_batch)
     if ev is not None:
@@ -465,6 +577,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         stream.foreachRDD(top.on_batch)
     if sil is not None:
         stream.foreachRDD(sil.on_batch)
+    if ex is not None:
+        stream.foreachRDD(ex.on_batch)
     ssc.start()
     try:
         ssc.awaitTermination()
@@ -479,8 +593,12 @@ def main(argv: Optional[List[str]] = None) -> int:
             top.close()
         if sil is not None:
             sil.close()
+        if ex is not None:
+            ex.close()
     if sil is not None:
         log.info("silhouette %s over %d batches", sil.total.silhouette, sil.batches)
+    if ex is not None:
+        log.info("selected %d exemplars per cluster of %d batches", ex.m, ex.batches)
     if ev is not None:
         log.info("evaluated %d batches", ev.batches)
     if top is not None:

@@ -20,7 +20,8 @@ short letters keep their meaning): ``--source``, ``--batchSize``,
 ``--resume``, ``--sourceRate``, ``--plotPoints``, ``--legacyNumTextFeatures``,
 ``--batchTimeout``, ``--checkReplicas``, ``--model``, ``--predictOut``,
 ``--scalerStd``, ``--evalOut``, ``--top``, ``--topSmallest`` (no value),
-``--topOut``, ``--silhouetteOut``.
+``--topOut``, ``--silhouetteOut``, ``--exemplars``, ``--exemplarsOut``,
+``--exemplarsFarthest`` (no value).
 The master accepts, besides Spark's ``local``, ``local[N]``, ``local[*]``
 (CPU plumbing engine, fp64), the device masters ``rocm``, ``rocm[N]``,
 ``rocm[*]`` and ``rocm:0,1,...`` (HIP engine, one process per GPU).
@@ -147,6 +148,8 @@ _EXT_FLAGS = {
     "--silhouetteOut": ("silhouetteOut", str),
     "--top": ("top", int),
     "--topOut": ("topOut", str),
+    "--exemplars": ("exemplars", int),
+    "--exemplarsOut": ("exemplarsOut", str),
     # apps/logistic_regression.py (and apps/score.py with a logistic model)
     "--labelThreshold": ("labelThreshold", int),
     "--threshold": ("threshold", float),
@@ -215,6 +218,9 @@ class ConfArguments:
         self.top = 0           # apps/score.py: select the N best rows of every batch (0: off)
         self.topSmallest = False   # ... the lowest values instead of the highest
         self.topOut = ""       # apps/score.py: directory of top.jsonl and summary.json
+        self.exemplars = 0     # apps/score.py, k-means models: the M rows nearest each centre, per batch (0: off)
+        self.exemplarsFarthest = False   # ... each cluster's farthest rows instead
+        self.exemplarsOut = ""  # apps/score.py: directory of exemplars.jsonl and summary.json
         # apps/logistic_regression.py: label = retweetCount >= labelThreshold (-1: middle of the
         # filter range), class 1 when the probability exceeds threshold
         self.labelThreshold = c.getInt("labelThreshold") if c.hasPath("labelThreshold") else -1
@@ -270,6 +276,12 @@ Usage: twtml-spark [options]
                                                   (MLlib's ClusteringEvaluator, squared Euclidean) against the
                                                   batch's own cluster means: silhouette.jsonl per batch,
                                                   summary.json: the row-weighted mean over the stream
+  --exemplars <M>  [--exemplarsFarthest]  --exemplarsOut <dir>
+                                                  scoring driver, k-means models: per cluster, the M (1..64,
+                                                  k M <= 2^18) tweets of every batch nearest its centre, selected
+                                                  on the device; --exemplarsFarthest: the cluster's own outliers.
+                                                  exemplars.jsonl per batch, summary.json: the best M per cluster
+                                                  of the stream (one distance scale only with --scalerStd)
   --scalerStd <file.npy>                          scoring driver, k-means models: the d column stds of a
                                                   frozen scaler (default: a StandardScaler fitted per batch)
   --labelThreshold <n>  --threshold <p>           logistic driver (apps.logistic_regression / twtml-logistic):
@@ -322,6 +334,10 @@ Usage: twtml-spark [options]
                 continue
             if flag == "--topSmallest":
                 self.topSmallest = True
+                i += 1
+                continue
+            if flag == "--exemplarsFarthest":
+                self.exemplarsFarthest = True
                 i += 1
                 continue
             if flag in _FLAG_LOOKUP and i + 1 < len(lst):

@@ -317,3 +317,21 @@ class CpuKMeans:
         out.update(dist2=out["values"], labels=labels, cost=res["cost"], sizes=res["sizes"], std=res["std"],
                    n_raw=res["n_raw"], n_scored=res["n_scored"], top_ms=ms, wall_ms=ms)
         return out
+
+    def exemplars_batch(self, raw: RawBatch, m: int, text_dims: int, largest: bool = False,
+                        apply_filter: bool = True, scaler="batch") -> Dict[str, object]:
+        """Per cluster, the m rows nearest their centre (``largest``: the
+        cluster's own outliers), the contract of
+        ``DeviceKMeans.exemplars_batch``: ``models/exemplars.cluster_top`` of
+        this engine's own ``predict_batch`` ``dist2`` and ``pred``, with the
+        batch's ``cost``, ``sizes`` and ``std``."""
+        from .exemplars import check_m, exemplars_result
+        k = self.state.centers.shape[0]
+        check_m(k, m)
+        t0 = time.perf_counter()
+        res = self.predict_batch(raw, text_dims, apply_filter=apply_filter, scaler=scaler)
+        out = exemplars_result(res["dist2"], res["pred"], res["rows"], k, m, largest)
+        ms = (time.perf_counter() - t0) * 1e3
+        out.update(dist2=out["values"], cost=res["cost"], sizes=res["sizes"], std=res["std"],
+                   n_raw=res["n_raw"], n_scored=res["n_scored"], ex_ms=ms, wall_ms=ms)
+        return out

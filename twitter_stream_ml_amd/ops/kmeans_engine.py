@@ -221,6 +221,43 @@ class DeviceKMeans:
                 "n_raw": int(r["n_raw"]), "n_scored": int(r["n_scored"]), "top_ms": float(r["top_ms"]),
                 "wall_ms": (time.perf_counter() - t0) * 1e3}
 
+    # ---- exemplars (KMEngine::exemplars, csrc/hip/exemplars.hip) ------------
+    def exemplars_batch(self, raw: RawBatch, m: int, largest: bool = False, apply_filter: bool = True,
+                        scaler="batch") -> Dict[str, object]:
+        """Per cluster, the m rows of one raw micro-batch nearest their centre
+        (the default: what the cluster is about; ``largest``: the cluster's own
+        outliers), selected on the device (the contract of
+        ``models/exemplars.py``): ``predict_batch``'s passes, then one top-m per
+        cluster over ``dist2`` -- ``counts`` (int64[k]), ``rows`` (int64[k, m],
+        -1 in unused entries) and ``dist2`` (= ``values``, fp64[k, m]), each
+        cluster best first, equal distances by ascending row; the batch's
+        ``cost``, ``sizes`` and ``std``; ``n_nan``, ``n_raw``, ``n_scored``,
+        ``ex_ms`` (device time of the whole pass; ``sel_ms``: of the selection
+        kernels alone) and ``wall_ms``.  Only these leave the device.
+        ``1 <= m <= 64`` and ``k * m <= 2**18``.  Arguments and guarantees are
+        ``predict_batch``'s."""
+        from ..models.exemplars import check_m, empty_exemplars
+        m = check_m(self.cfg.k, m)
+        mode, std = scaler_mode(scaler, self.dim, bool(self.cfg.scale))
+        if raw.n == 0:                # nothing is staged or launched
+            e = empty_score(0, self.cfg.k, std)
+            out = empty_exemplars(self.cfg.k, m)
+            return {**out, "dist2": out["values"], "cost": 0.0, "sizes": e["sizes"], "std": e["std"], "n_raw": 0,
+                    "n_scored": 0, "ex_ms": 0.0, "sel_ms": 0.0, "wall_ms": 0.0}
+        t0 = time.perf_counter()
+        slot = self._pipe.free_slot()
+        try:
+            self.submit(self._stage(slot, raw), slot)
+            r = self._eng.exemplars(int(slot), bool(apply_filter), mode, std, m, bool(largest))
+        finally:
+            self._pipe.score_done(slot)
+        values = np.asarray(r["values"])
+        return {"counts": np.asarray(r["counts"]), "rows": np.asarray(r["rows"]), "values": values, "dist2": values,
+                "n_nan": int(r["n_nan"]), "cost": float(r["cost"]), "sizes": np.asarray(r["sizes"]),
+                "std": std.copy() if std is not None else (np.asarray(r["std"]) if len(r["std"]) else None),
+                "n_raw": int(r["n_raw"]), "n_scored": int(r["n_scored"]), "ex_ms": float(r["ex_ms"]),
+                "sel_ms": float(r["sel_ms"]), "wall_ms": (time.perf_counter() - t0) * 1e3}
+
     # ---- silhouette (KMEngine::silhouette, csrc/hip/silhouette.hip) --------
     def silhouette_batch(self, raw: RawBatch, apply_filter: bool = True, scaler="batch",
                          per_row: bool = False) -> Dict[str, object]:
